@@ -1,6 +1,7 @@
 """EfficientDet-D0 bf16 train-step throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--dtype bf16]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -9,7 +10,23 @@ gradient all-reduce when N>1, L2 + clip + SGD-momentum + EMA, BN moving statisti
 synthetic 512x512 batch of 32 images per GPU (weak scaling).  Inputs and targets are resident
 in HBM before the timed region.  The step is captured once in a HIP graph and replayed.
 
-Prints ONE JSON line on rank 0 with value = images/s over all ranks, plus
+Prints ONE JSON line on rank 0 with value = images/s over all ranks and ms_per_step = the
+milliseconds one of the K timed steps took.  A plain run sets up, warms up, times the K steps
+and prints that line.
+
+--dump-outputs DIR writes what the timed path computes (rank 0) as DIR/<name>.npy, float32: the
+step's loss and gradient norm, its flat gradient, and the state it leaves (weights, EMA weights,
+BN moving statistics); for the backbone workload the last timed step's feature maps.  Above 60 MB
+in all, every array is cut to a fixed seeded sample of its elements.  Inputs, targets and initial
+parameters are seeded, so two builds run with the same arguments can be compared array for array.
+The train step's inputs include the model state, and the state the last timed step starts from
+is not the same every run: the steps train on one batch, and the order of the weight gradients'
+fp32 atomics (last-bit differences in one step) moves that trajectory further with every update
+(DESIGN.md).  So after the timed steps the seeded initial state is put back and the timed path
+(the same captured graph) runs once more for the dump, outside the timed region: what it writes
+is the step on identical inputs, the same every run up to that last-bit summation order.
+
+--full adds, after the timed steps (runs of their own; the fields are null without it):
   roofline       : the device kernel with the most time in the step (by base name; the
                    library reports which kernel each call launched): its algorithmic bytes per
                    launch / its average launch duration, timed by wall-clock probes around its
@@ -36,6 +53,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0
+DUMP_BUDGET_BYTES = 60_000_000
 
 
 def log(*a):
@@ -59,6 +77,23 @@ def synthetic_batch(anchors, B, size, seed, device, dtype):
             boxes[b, k] = [cy - h / 2, cx - w / 2, cy + h / 2, cx + w / 2]
     t = anchors.generate_targets_batched(torch.tensor(boxes), torch.tensor(cls), torch.full((B,), G, dtype=torch.int32))
     return x, t
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of ``arrays`` as <dirname>/<name>.npy in float32.  When they
+    exceed DUMP_BUDGET_BYTES together, every array keeps the same share of its elements, at
+    indices drawn once from a fixed seed (flat, ascending), so two runs keep the same ones."""
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(4 * a.numel() for a in arrays.values())
+    rng = np.random.default_rng(0)
+    for name, a in arrays.items():
+        a = a.detach()
+        if total > DUMP_BUDGET_BYTES:
+            a = a.reshape(-1)
+            k = max(1, a.numel() * DUMP_BUDGET_BYTES // total)
+            idx = np.sort(rng.choice(a.numel(), k, replace=False))
+            a = a[torch.from_numpy(idx).to(a.device)]
+        np.save(os.path.join(dirname, name + ".npy"), a.float().cpu().numpy())
 
 
 # ---------------------------------------------------------------- per-kernel instrumentation
@@ -619,11 +654,15 @@ def bench_backbone(args):
     for _ in range(2):
         model.backbone(x, training=False)
     torch.cuda.synchronize()
-    step = lambda: model.backbone(x, training=False)  # noqa: E731
+    feats = []  # the last step's [features, reduction_1..5]
+
+    def step():
+        feats[:] = model.backbone(x, training=False)
+
     if args.graph:
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            model.backbone(x, training=False)
+            step()  # every replay writes the captured feature maps in place
         step = g.replay
     for _ in range(args.warmup):
         step()
@@ -631,8 +670,10 @@ def bench_backbone(args):
     el = dp.max_over_ranks(ctx, el, dev)
     value = world * B * args.steps / el
     log(f"[bench] backbone B0@224 B={B}/gpu: {args.steps} steps in {el:.3f}s -> {value:.1f} img/s")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {("features" if i == 0 else f"reduction_{i}"): f for i, f in enumerate(feats)})
     roofline = table = step_level = kernels = None
-    if args.kernel_timing and rank == 0:
+    if args.full and args.kernel_timing and rank == 0:
         roofline, table, step_level, kernels = kernel_tables(lambda: model.backbone(x, training=False), args, el)
     if rank == 0:
         print(json.dumps({
@@ -657,8 +698,12 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--model", default="efficientdet-d0")
     ap.add_argument("--graph", type=int, default=1)
-    ap.add_argument("--cpu-baseline", type=int, default=1)
-    ap.add_argument("--kernel-timing", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the per-kernel roofline legs and the CPU baseline")
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="with --full: 0 leaves the CPU baseline out")
+    ap.add_argument("--kernel-timing", type=int, default=1, help="with --full: 0 leaves the roofline legs out")
     ap.add_argument("--overlap", type=int, default=0, help="weight gradients on a side stream")
     ap.add_argument("--workload", default="train", choices=["train", "backbone"],
                     help="train: the headline D0 train step; backbone: BASELINE config 2 (B0 @224 forward)")
@@ -698,6 +743,9 @@ def main():
     data = (x, t)
     log(f"[bench] {args.model} B={B}/gpu world={world} dtype={args.dtype} params={model.P.n_trainable}")
 
+    state = (model.P.w, model.P.v, model.P.ema, model.P.bn_mm, model.P.bn_mv, model.step_counter)
+    state0 = [t.clone() for t in state] if args.dump_outputs else None  # the seeded initial state
+
     # eager warm-up (allocates persistent buffers), then capture
     for _ in range(2):
         model.train_step(data)
@@ -727,9 +775,26 @@ def main():
     loss = float(lt) - (world - 1) * l2
     gnorm = float(model.scalars[3])
     log(f"[bench] {args.steps} steps in {el:.3f}s -> {value:.1f} img/s  loss={loss:.4f} gnorm={gnorm:.4f}")
+    if args.dump_outputs:
+        # the timed path once more, from the seeded initial state (every rank: the step holds the
+        # all-reduces); the state the timed steps left is put back for what follows
+        P = model.P
+        left = [t.clone() for t in state]
+        for t, c in zip(state, state0):
+            t.copy_(c)
+        P.refresh_compute_copy()
+        step()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"loss": model.scalars[0:1], "gnorm": model.scalars[3:4],
+                                             "gradients": P.g, "weights": P.w, "ema_weights": P.ema,
+                                             "bn_moving_mean": P.bn_mm, "bn_moving_variance": P.bn_mv})
+        for t, c in zip(state, left):
+            t.copy_(c)
+        P.refresh_compute_copy()
 
     roofline = kernels = table = step_level = None
-    if args.kernel_timing and rank == 0:
+    if args.full and args.kernel_timing and rank == 0:
         # the instrumented steps below run on rank 0 alone: snapshot the optimizer-visible
         # state and restore it afterwards so rank 0 leaves in step with the other replicas
         P = model.P
@@ -746,7 +811,7 @@ def main():
         model.grad_allreduce, model.npos_allreduce = ar, ar
 
     cpu = None
-    if args.cpu_baseline and rank == 0 and world == 1:
+    if args.full and args.cpu_baseline and rank == 0 and world == 1:
         log("[bench] cpu baseline (oracle, fp32) ...")
         cpu = cpu_baseline(model, anchors)
         log(f"[bench] cpu baseline {cpu['value']:.3f} img/s on {cpu['cores']} threads")

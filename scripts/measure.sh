@@ -3,7 +3,7 @@
 #   1. PMC traffic, two passes (FETCH_SIZE, WRITE_SIZE)      -> pmc_traffic.json / _pmc_traffic.txt
 #   2. PMC MFMA utilisation (SQ_VALU_MFMA_BUSY_CYCLES)       -> pmc_mfma.json / _pmc_mfma.txt
 #   2b. PMC wave-time breakdown + instruction mix, two passes -> pmc_limiter.json / _pmc_limiter.txt
-#   3. the default bench line, with the JSONs of 1-2 in profiles/ so its table reads them
+#   3. the default bench line with --full, with the JSONs of 1-2 in profiles/ so its table reads them
 #   4. rocprofv3 --kernel-trace --stats of the same bench command
 #   5. scripts/kbench.py per-launch replay table
 # Every GPU step has its own time limit and the steps are chained: the first failure ends it.
@@ -34,9 +34,9 @@ timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_IN
 python scripts/pmc_limiter.py --a $O/pmc_lima --b $O/pmc_limb --steps 6 --tag $TAG --out $O/pmc_limiter.json \
     > $O/${TAG}_pmc_limiter.txt &&
 cp $O/pmc_traffic.json $O/pmc_mfma.json $O/pmc_limiter.json profiles/ &&
-timeout -k 10 900 python bench.py $BENCH > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log &&
+timeout -k 10 900 python bench.py $BENCH --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.log &&
 timeout -k 10 900 rocprofv3 --kernel-trace --stats -d $O/ktrace -o run --output-format csv \
-    -- python bench.py $BENCH --cpu-baseline 0 > $O/ktrace.log 2>&1 &&
+    -- python bench.py $BENCH --full --cpu-baseline 0 > $O/ktrace.log 2>&1 &&
 cp $(find $O/ktrace -name "*kernel_stats.csv" | head -1) $O/${TAG}_kernel_stats.csv &&
 timeout -k 10 300 python scripts/kbench.py --top 400 --out $O/${TAG}_kbench.txt > /dev/null 2> $O/kbench.err
 rc=$?

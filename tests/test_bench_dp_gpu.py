@@ -4,7 +4,7 @@ The driver's 8-GPU scaling run (BASELINE config 4) launches
 
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-and that branch -- the three captured graphs with the N+ and gradient all-reduces between them
+(here with --full, for rank 0's instrumented steps) and that branch -- the three captured graphs with the N+ and gradient all-reduces between them
 (`dist.graphed_train_step`), rank 0's instrumented steps with the state snapshot and restore,
 the global-loss reduction and `max_over_ranks` -- is run here exactly so, with torchrun as the
 launcher, two ranks sharing cuda:0 over gloo (`EDET_DP_BACKEND=gloo`; RCCL needs one GPU per
@@ -43,7 +43,7 @@ def test_bench_two_ranks_torchrun_gloo(tmp_path):
     env = dict(os.environ, EDET_DP_BACKEND="gloo", EDET_BENCH_DUMP=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1"]
+           "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     # rank 0's progress goes to a file as it runs (a report directory when one is given)
     logdir = os.environ.get("EDET_REPORT_DIR") or str(tmp_path)
     os.makedirs(logdir, exist_ok=True)

@@ -6,7 +6,7 @@
 # STEPS (run in order, the first failure ends the call):
 #   suite    pytest -m gpu (parity reports under $O/parity) + __graft_entry__.smoke()
 #   tests    pytest -m gpu -k "$K" only (TESTS_K), no reports
-#   bench    bench.py with the default arguments
+#   bench    bench.py --full with the default arguments
 #   measure  scripts/measure.sh: PMC traffic + MFMA passes, bench, rocprof kernel stats, kbench
 #   configs  BASELINE config 2 (B0 backbone 224, B = 64) and config 5 (D4 1024, B = 8) bench lines
 #   kbench   scripts/kbench.py per-launch table only (KB_ARGS passed through)
@@ -32,15 +32,15 @@ for step in $STEPS; do
           -k "${TESTS_K:-}" > $O/pytest_k.log 2>&1
       rc=$?; tail -5 $O/pytest_k.log; [ $rc -eq 0 ] || exit $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > $O/bench.json 2> $O/bench.log
+      timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.log
       rc=$?; tail -3 $O/bench.log; cut -c1-300 $O/bench.json; [ $rc -eq 0 ] || exit $rc ;;
     measure)
       env -u STEPS TAG=$TAG bash scripts/measure.sh > $O/measure.log 2>&1
       rc=$?; tail -8 $O/measure.log; [ $rc -eq 0 ] || exit $rc ;;
     configs)
-      timeout -k 10 400 python bench.py --workload backbone --batch 64 --steps 20 --warmup 5 --cpu-baseline 0 \
+      timeout -k 10 400 python bench.py --workload backbone --batch 64 --steps 20 --warmup 5 --full --cpu-baseline 0 \
           > $O/${TAG}_config2_backbone_b64_bench.json 2> $O/config2.log &&
-      timeout -k 10 600 python bench.py --model efficientdet-d4 --batch 8 --steps 10 --warmup 3 --cpu-baseline 0 \
+      timeout -k 10 600 python bench.py --model efficientdet-d4 --batch 8 --steps 10 --warmup 3 --full --cpu-baseline 0 \
           > $O/${TAG}_config5_d4_b8_1gpu_bench.json 2> $O/config5.log
       rc=$?
       cut -c1-200 $O/${TAG}_config2_backbone_b64_bench.json $O/${TAG}_config5_d4_b8_1gpu_bench.json
