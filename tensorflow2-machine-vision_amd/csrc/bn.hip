@@ -224,12 +224,15 @@ __global__ __launch_bounds__(256) void k_lazy_bwd_reduce(LArgs g, int nchunks) {
           }
 #pragma unroll
           for (int u = 0; u < EUR; ++u) {
-            const float k = m + u * geo.R < m_end ? dvs[u] : 0.f;
+            // rows past the chunk's end add nothing; an image whose drop-connect scale is 0 still
+            // carries its dsq term (as k_lazy_bwd_apply)
+            const bool live = m + u * geo.R < m_end;
+            const float k = live ? dvs[u] : 0.f;
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
               float gg = d[u][j] * k;
               if (F & AF_GATE) gg *= gt[u][j];
-              if (F & AF_DSQ) gg += ds[u][j] * (k != 0.f ? 1.f : 0.f);
+              if (F & AF_DSQ) gg += live ? ds[u][j] : 0.f;
               const float du = (F & AF_ACT) ? gg * dswishf_(x[u][j] * sc[j] + sh[j]) : gg;
               s[v][j] += du;
               q[v][j] += du * ((x[u][j] - mu_[j]) * rs[j]);

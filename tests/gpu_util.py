@@ -1,5 +1,6 @@
 """Helpers for the GPU parity tests: descriptors for raw tensors and CPU fp64 references."""
 import ctypes
+import os
 
 import numpy as np
 import torch
@@ -38,6 +39,25 @@ class LazyDesc:
                 lz.bn.sum[s], lz.bn.sq[s], lz.bn.gamma[s], lz.bn.beta[s] = ra.data_ptr(), rb.data_ptr(), c.data_ptr(), d.data_ptr()
         self.c = lz
 
+    def cpu_rows(self, sl):
+        """fp64 value of the rows sl of a single-segment tensor (sl inside the segment): the
+        row-blocked form of cpu_value for tensors whose fp64 copy would not fit the host."""
+        assert self.pyr.nseg == 1
+        v = self.x[sl, : self.C].double().cpu()
+        if self.bn:
+            su, sq, ga, be = (t.double().cpu() for t in self.bn[0])
+            n = self.pyr.seg_rows(0)
+            mean = su / n
+            var = torch.clamp(sq / n - mean * mean, min=0)
+            v = (v - mean) / torch.sqrt(var + self.eps) * ga + be
+        if self.act:
+            v = v * torch.sigmoid(v)
+        if self.gate is not None:
+            hw = self.pyr.sizes[0][0] * self.pyr.sizes[0][1]
+            img = torch.arange(sl.start, sl.stop) // hw
+            v = v * self.gate.double().cpu()[img]
+        return v
+
     def cpu_value(self):
         x = self.x[:, : self.C].double().cpu()
         out = x.clone()
@@ -63,15 +83,78 @@ class LazyDesc:
 def make_bn(x, pyr: Pyr, C, rng, shift=0.0):
     """Random BN params and *exact* batch stats of x per segment (fp32 device)."""
     segs = []
-    xc = x[:, :C].double().cpu()
     for s in range(pyr.nseg):
-        v = xc[pyr.seg_slice(s)]
-        su = v.sum(0).to(DEV)  # fp64 statistics arena (edet_bn.sum / sq)
-        sq = (v * v).sum(0).to(DEV)
+        sl = pyr.seg_slice(s)
+        su = torch.zeros(C, dtype=torch.float64)
+        sq = torch.zeros(C, dtype=torch.float64)
+        for b in row_blocks(sl.start, sl.stop):  # one block up to 2^18 rows: the plain fp64 sums
+            v = x[b, :C].double().cpu()
+            su += v.sum(0)
+            sq += (v * v).sum(0)
+        su, sq = su.to(DEV), sq.to(DEV)  # fp64 statistics arena (edet_bn.sum / sq)
         ga = torch.tensor(rng.uniform(0.5, 1.5, C), dtype=torch.float32, device=DEV)
         be = torch.tensor(rng.uniform(-0.5, 0.5, C) + shift, dtype=torch.float32, device=DEV)
         segs.append((su, sq, ga, be))
     return segs
+
+
+def row_blocks(start, stop, step=1 << 18):
+    """Row slices of at most `step` rows covering [start, stop): fp64 references of the long
+    tensors are built block by block so the host never holds a whole fp64 copy."""
+    return [slice(a, min(stop, a + step)) for a in range(start, stop, step)]
+
+
+def ref_threads():
+    """CPU threads for the fp64 references (as test_headline_gpu.py)."""
+    torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
+
+
+def ints(rng, shape, lo, hi, dt, keep=1.0):
+    """Integers of [lo, hi] in the storage type (exact in bf16), a fraction `keep` of them
+    nonzero: operands of the exact-sum cases."""
+    v = rng.integers(lo, hi + 1, size=shape)
+    if keep < 1.0:
+        v = v * (rng.random(shape) < keep)
+    return g(torch.tensor(v, dtype=torch.float32), dt)
+
+
+def routed(name, *args):
+    """L.call(name, *args); returns the base names of the kernels that call launched."""
+    L.launched_kernels()
+    L.call(name, *args)
+    return L.launched_kernels()
+
+
+def dswish(u):
+    s = torch.sigmoid(u)
+    return s * (1 + u * (1 - s))
+
+
+class BnBwdClosedForm:
+    """Training-mode BN backward of v = act(bn(x)) over one segment in closed form (fp64), in
+    row blocks:  du = dv * act'(u),  dbeta = sum du,  dgamma = sum du * xhat,
+    dx = gamma * rstd * (du - dbeta / n - xhat * dgamma / n).
+    add() takes every block once (the sums); dx() then gives a block's input gradient."""
+
+    def __init__(self, su, sq, gamma, beta, n, eps=1e-3, act=0):
+        self.n, self.act, self.gamma, self.beta = n, act, gamma, beta
+        self.mean = su / n
+        self.rstd = 1.0 / torch.sqrt(torch.clamp(sq / n - self.mean * self.mean, min=0) + eps)
+        self.dbeta = torch.zeros_like(su)
+        self.dgamma = torch.zeros_like(su)
+
+    def _du(self, x, dv):
+        xhat = (x - self.mean) * self.rstd
+        return (dv * dswish(xhat * self.gamma + self.beta) if self.act else dv), xhat
+
+    def add(self, x, dv):
+        du, xhat = self._du(x, dv)
+        self.dbeta += du.sum(0)
+        self.dgamma += (du * xhat).sum(0)
+
+    def dx(self, x, dv):
+        du, xhat = self._du(x, dv)
+        return self.gamma * self.rstd * (du - self.dbeta / self.n - xhat * (self.dgamma / self.n))
 
 
 def zeros64(*shape):

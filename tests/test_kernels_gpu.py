@@ -555,7 +555,10 @@ def test_dwconv_long_blocks(k, s, B, H, C):
                                                         (144, 1, 0, 0, 0, 1), (24, 0, 0, 0, 0, 1), (240, 1, 1, 0, 0, 1),
                                                         (672, 1, 1, 1, 0, 1), (672, 1, 0, 0, 0, 1),
                                                         # the channel-sliced apply (C >= 1024, M <= 16384)
-                                                        (1152, 1, 1, 1, 0, 1), (1152, 1, 0, 0, 1, 2)])
+                                                        (1152, 1, 1, 1, 0, 1), (1152, 1, 0, 0, 1, 2),
+                                                        # drop-connect scale and the SE squeeze term together,
+                                                        # one image dropped (scale 0): its dsq term stays
+                                                        (96, 1, 1, 1, 1, 1)])
 def test_lazy_backward(dt, C, act, gate, dsq, scale, nseg):
     rng = np.random.default_rng(C + act * 7 + nseg)
     B = 3
@@ -573,6 +576,8 @@ def test_lazy_backward(dt, C, act, gate, dsq, scale, nseg):
     dv = pyr_data(rng, pyr, C, dt)
     dsqt = g(rnd(rng, B, C) * 0.1, "f32") if dsq else None
     sc = g(torch.tensor(rng.choice([0.0, 1.25], size=(nseg, B)), dtype=torch.float32), "f32") if scale else None
+    if scale and dsq:  # a dropped image and a kept one, whatever the draw
+        sc[0, 0], sc[0, 1] = 0.0, 1.25
     grads = [(zeros(C), zeros(C)) for _ in range(nseg)]
     so = seg_out(grads)
     acc_t, acc = bngrad64(nseg, C)
@@ -581,6 +586,9 @@ def test_lazy_backward(dt, C, act, gate, dsq, scale, nseg):
     L.call("edet_lazy_bwd_apply", DT[dt], lz.c, pyr.c, C, vp(dv), vp(sc), vp(dsqt), acc, so, vp(dx), 0, stream())
     for sg in range(nseg):  # fp32 parameter gradients are the fp64 sums, written once
         assert torch.equal(grads[sg][0], acc_t[0, sg].float()) and torch.equal(grads[sg][1], acc_t[1, sg].float())
+    # the accumulating instantiations: dx += the same gradient, into a dx holding 0.5
+    dxa = g(torch.full((pyr.rows, C), 0.5), dt)
+    L.call("edet_lazy_bwd_apply", DT[dt], lz.c, pyr.c, C, vp(dv), vp(sc), vp(dsqt), acc, None, vp(dxa), 1, stream())
     # reference: autograd through BN(train, batch stats recomputed) -> act -> gate, with dsq term
     xc = x.double().cpu()
     for sg in range(nseg):
@@ -604,6 +612,8 @@ def test_lazy_backward(dt, C, act, gate, dsq, scale, nseg):
             d = d + dsqt.double().cpu().repeat_interleave(hw, 0)
         (a * d).sum().backward()
         close(dx[sl], xs.grad, dt, scale=4)
+        # (old + dx) rounds once to the storage type: the bf16 bar of test_conv1x1_dgrad
+        close(dxa[sl], xs.grad + 0.5, dt, **(dict(scale=4) if dt == "f32" else dict(rtol=5e-3, atol=5e-3)))
         close(grads[sg][1], be.grad, dt, scale=n ** 0.5 * 2)
         close(grads[sg][0], ga.grad, dt, scale=n ** 0.5 * 2)
 
