@@ -434,6 +434,45 @@ int edet_detect_nms(int dtype, const float* boxes, const void* cls, int ldc, con
                     float* out_boxes, int32_t* out_cls, float* out_scores, int32_t* out_count,
                     edet_stream_t stream);
 
+/* Per-class detection post-processing of a batch: the multi-label protocol of the published
+ * EfficientDet evaluation, opt-in next to edet_detect_nms (which stays the reference's
+ * convert_outputs_one).  Three launches: a chip-wide threshold scan of the logits in two passes
+ * (count, then ordered write) and one block per image for sort + per-class NMS.
+ *
+ * Inputs: box [rows][ldb] raw regressions in dtype, channel a*4 + j (not decoded: only the
+ * candidates' boxes are, with edet_decode_boxes' arithmetic); cls [rows][ldc] logits in dtype,
+ * channel a*NC + c; anchors fp32 [N][4] and the pyramid as for edet_decode_boxes, N =
+ * sum_l H_l*W_l*A < 2^24.
+ *
+ * Candidates of image n: every (anchor i, class c) with 1 <= c < NC (class 0 is background)
+ * and fp32(logit) >= logit_thr; for a score threshold s the caller passes the fp32 rounding of
+ * log(s / (1 - s)) evaluated in fp64 (-inf admits every logit).  i is the anchor's index in
+ * the image's concatenated [level][H][W][A] order and i*NC + c the candidate's flat id.  At most max_candidates (1..EDET_DETECT_MAX_CANDIDATES)
+ * enter NMS: with more, the first max_candidates in ascending flat id do and out_overflow[n]
+ * = 1 (else 0); out_total[n] is the number found either way.  No outcome depends on the order
+ * of atomic operations.
+ *
+ * NMS: within each class, in (logit descending, anchor index ascending) order, a candidate is
+ * kept if no earlier kept candidate of its class overlaps it by >= iou_thr; metric selects the
+ * overlap, EDET_OVERLAP_IOU or EDET_OVERLAP_DIOU (the measures of generate_targets and of
+ * edet_detect_nms).  A class keeps at most max_out boxes (1..max_candidates).
+ *
+ * Output: of an image's kept candidates the first max_out by (logit descending, anchor index
+ * ascending, class ascending): out_boxes [batch][max_out][4] (y1,x1,y2,x2), out_cls and
+ * out_scores [batch][max_out] (scores 1/(1+expf(-logit))), out_count [batch]; rows past
+ * out_count[n] are unspecified.
+ *
+ * scratch (8-byte aligned): batch * (8*max_candidates + 4*sum_l ceil(H_l*W_l /
+ * EDET_DETECT_CHUNK_ROWS)) bytes.  NC <= 256; ldc >= A*NC; ldb >= 4*A. */
+#define EDET_DETECT_MAX_CANDIDATES 4096 /* 8 B key + 16 B box each in the NMS block's LDS: 96 KiB */
+#define EDET_DETECT_CHUNK_ROWS 16       /* pyramid rows per block of the scan */
+enum { EDET_OVERLAP_IOU = 0, EDET_OVERLAP_DIOU = 1 };
+int edet_detect_per_class(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                          const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
+                          float logit_thr, int metric, void* scratch, float* out_boxes, int32_t* out_cls,
+                          float* out_scores, int32_t* out_count, int32_t* out_total, int32_t* out_overflow,
+                          edet_stream_t stream);
+
 /* ---- optimizer: L2 + clip_by_global_norm + SGD momentum + EMA, fused ----
  * scalars: [0] loss  [1] sum g^2  [2] sum w^2 (L2 params)  [3] gnorm  [4] lr  [5] npos
  *          [6] 1 when edet_opt_apply skipped a non-finite step (sched->skip_nonfinite), else 0

@@ -6,6 +6,7 @@ steady-state duration is measured without the eager launch gaps of a single-even
 Replays re-run accumulating kernels (values drift; irrelevant for timing).
 
   python scripts/kbench.py [--reps 10] [--filter conv1x1] [--top 80] [--batch 32]
+  python scripts/kbench.py --detect [--batch 1]     the two detection post-processing paths
 """
 import argparse
 import os
@@ -19,8 +20,51 @@ import torch  # noqa: E402
 import bench  # noqa: E402
 
 
+def detect_bench(args):
+    """Anchors.detect_per_class (scan, ordered write, per-class NMS) against convert_outputs_boxes
+    + Anchors.detect on the same bf16 D0 tensors: random logits N(-6.43, 1), about 1 000 of an
+    image's 49 104 x 80 foreground logits at or above the 0.05 score threshold.  The reference
+    path gets the same threshold (in its logit units) and output size.  Median of 9 windows of
+    --reps back-to-back calls between two events, after a warm-up."""
+    import math
+    import numpy as np
+    from tf2mv_amd.anchors import Anchors
+    from tf2mv_amd.config import get_efficientdet_config
+    dev = torch.device("cuda", 0)
+    cfg = get_efficientdet_config(args.model)
+    S, B, A, NC = cfg.image_size, args.batch, cfg.num_scales * len(cfg.aspect_ratios), cfg.num_classes
+    an = Anchors(cfg.min_level, cfg.max_level, (S, S), cfg.num_scales, cfg.aspect_ratios, cfg.anchor_scale, device=dev)
+    pyr = an.pyramid(B)
+    g = torch.Generator(device=dev).manual_seed(0)
+    rel = (0.3 * torch.randn(pyr.rows, A * 4, device=dev, generator=g)).bfloat16()
+    lg = (torch.randn(pyr.rows, A * NC, device=dev, generator=g) - 6.43).bfloat16()
+    bl = tuple(rel[pyr.seg_slice(s)].view(B, h, w, A, 4) for s, (h, w) in enumerate(an.level_sizes))
+    cl = tuple(lg[pyr.seg_slice(s)].view(B, h, w, A, NC) for s, (h, w) in enumerate(an.level_sizes))
+    t = math.log(0.05 / 0.95)
+    paths = {"per_class": lambda: an.detect_per_class(bl, cl, 100, 0.5, 0.05, "iou"),
+             "reference": lambda: an.detect(an.convert_outputs_boxes(bl), cl, 100, 0.5, t)}
+    out = paths["per_class"]()
+    print(f"detect D0 {S}x{S} NC={NC} bf16 B={B}: candidates per image {out[4].tolist()}, kept {out[3].tolist()}; "
+          f"reference path kept {paths['reference']()[3].tolist()}")
+    reps = max(args.reps, 50)
+    for name, fn in paths.items():
+        for _ in range(10):
+            fn()
+        us = []
+        for _ in range(9):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                fn()
+            e.record()
+            torch.cuda.synchronize()
+            us.append(s.elapsed_time(e) * 1e3 / reps)
+        print(f"  {name:10s} median {np.median(us):8.1f} us  (min {min(us):.1f}, max {max(us):.1f}; {reps} calls x 9)")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--detect", action="store_true", help="time the detection post-processing paths and exit")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--filter", default="")
     ap.add_argument("--top", type=int, default=80)
@@ -32,6 +76,8 @@ def main():
     ap.add_argument("--abi-any", action="store_true",
                     help="A/B against an older build (EDET_LIB): accept its ABI version, drop entry points it lacks")
     args = ap.parse_args()
+    if args.detect:
+        return detect_bench(args)
     if args.abi_any:
         import ctypes
         from tf2mv_amd import _lib as L0

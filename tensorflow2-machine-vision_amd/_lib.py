@@ -51,6 +51,8 @@ def stat_unfold(v):
     pad[..., :C] = v
     o[..., 0, :] = pad.view(*lead, -1, 16)
     return out
+DETECT_MAX_CANDIDATES, DETECT_CHUNK_ROWS = 4096, 16  # EDET_DETECT_MAX_CANDIDATES, EDET_DETECT_CHUNK_ROWS
+OVERLAP = {"iou": 0, "diou": 1}  # EDET_OVERLAP_IOU, EDET_OVERLAP_DIOU
 ACT_NONE, ACT_SWISH = 0, 1
 MODE_SAME, MODE_UPSAMPLE, MODE_MAXPOOL = 0, 1, 2
 
@@ -183,6 +185,8 @@ SIGNATURES = {
     "edet_generate_targets": [P, PPyr, c_int, P, P, P, c_int, c_float, P, P, P, P],
     "edet_decode_boxes": [c_int, P, PPyr, c_int, P, c_int, P, P],
     "edet_detect_nms": [c_int, P, P, c_int, PPyr, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P],
+    "edet_detect_per_class": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float, c_float,
+                              c_int, P, P, P, P, P, P, P, P],
     "edet_opt_norm": [P, P, c_int64, c_int64, PSched, P, P, P, P],
     "edet_opt_apply": [P, P, P, P, c_int64, c_int64, PSched, P, P, c_int, P, P, P],
     "edet_cast_f32": [c_int, P, P, c_int64, P],

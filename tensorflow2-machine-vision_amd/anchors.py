@@ -207,6 +207,45 @@ class Anchors:
                float(score_threshold), vp(scratch), vp(ob), vp(oc), vp(os_), vp(cnt), stream())
         return ob, oc, os_, cnt
 
+    def detect_per_class(self, outputs_boxes, outputs_classes, max_output_size: int = 100,
+                         iou_threshold: float = 0.5, score_threshold: float = 0.05, metric: str = "iou",
+                         max_candidates: int = L.DETECT_MAX_CANDIDATES):
+        """Multi-label, per-class post-processing (include/edet.h, edet_detect_per_class): every
+        (anchor, class >= 1) pair with sigmoid(logit) >= score_threshold is a candidate, greedy
+        NMS (``metric`` "iou" or "diou") runs within each class, and the image's best
+        max_output_size kept candidates are returned by (score desc, anchor, class).
+
+        outputs_boxes / outputs_classes: the raw per-level regressions [B,H,W,A,4] and logits
+        [B,H,W,A,NC] as returned by EfficientDetNet.call (boxes NOT decoded: only the
+        candidates' are, inside the kernel).  At most max_candidates candidates per image enter
+        NMS, the first in flat (anchor, class) order.  Returns (boxes [B,max,4], class ids
+        [B,max], scores [B,max], counts [B], total [B] candidates found, overflow [B] 1 where
+        total > max_candidates); rows past counts[b] are unspecified."""
+        if metric not in L.OVERLAP:
+            raise ValueError(f"metric {metric!r}: expected one of {sorted(L.OVERLAP)}")
+        if not 0.0 <= score_threshold < 1.0:
+            raise ValueError(f"score_threshold {score_threshold} outside [0, 1)")
+        # the comparison runs in logit space: fp32(log(s / (1 - s))) from fp64
+        logit_thr = float(np.float32(np.log(score_threshold / (1.0 - score_threshold)))) if score_threshold else -np.inf
+        B = outputs_classes[0].shape[0]
+        NC = outputs_classes[0].shape[-1]
+        A = self.get_anchors_per_location()
+        pyr = self.pyramid(B)
+        bptr, bld, bdt = _pyramid_base(outputs_boxes, pyr)
+        cptr, cld, cdt = _pyramid_base(outputs_classes, pyr)
+        assert bdt == cdt, "regressions and logits must share the model dtype"
+        dev = self.device
+        nbi = sum(-(-h * w // L.DETECT_CHUNK_ROWS) for h, w in self.level_sizes)
+        scratch = torch.empty(B * (2 * max(max_candidates, 0) + nbi), dtype=torch.int32, device=dev)
+        ob = torch.empty((B, max_output_size, 4), dtype=torch.float32, device=dev)
+        oc = torch.empty((B, max_output_size), dtype=torch.int32, device=dev)
+        os_ = torch.empty((B, max_output_size), dtype=torch.float32, device=dev)
+        cnt, total, over = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+        L.call("edet_detect_per_class", cdt, vp(self.flat), bptr, bld, cptr, cld, pyr.c, A, NC, max_candidates,
+               max_output_size, float(iou_threshold), logit_thr, L.OVERLAP[metric], vp(scratch),
+               vp(ob), vp(oc), vp(os_), vp(cnt), vp(total), vp(over), stream())
+        return ob, oc, os_, cnt, total, over
+
     def convert_outputs_one(self, batch_index: int, outputs_boxes, outputs_classes):
         """anchors.py:161-202 signature: (boxes [k,4], class ids [k], scores [k]) of one image."""
         ob, oc, os_, cnt = self.detect(outputs_boxes, outputs_classes)

@@ -1,0 +1,425 @@
+// Per-class detection post-processing (edet_detect_per_class): the multi-label protocol of the
+// published EfficientDet evaluation.  Every (anchor, class >= 1) pair whose logit reaches the
+// threshold is a candidate; NMS suppresses within a class only.
+//
+//   k_cand_count / k_cand_write   chip-wide threshold scan of the logits with an ordered
+//                                 compaction: blocks own contiguous row chunks numbered in flat
+//                                 (image, level, row) order, pass 1 counts, pass 2 sums the counts
+//                                 of the blocks before it and writes its survivors in place
+//   k_nms_pc                      one block per image: LDS bitonic sort by (class, logit desc,
+//                                 anchor), decode of the candidates' boxes only, wave-parallel
+//                                 greedy NMS per class out of LDS, final sort by score
+//
+// No floating-point atomics and no order-dependent integer atomics: the candidate list, and so
+// every output, is a function of the inputs alone.
+#pragma clang fp contract(off)
+#include "boxes.hpp"
+
+namespace edet {
+
+constexpr int DET_CH = EDET_DETECT_CHUNK_ROWS;  // pyramid rows per scan block
+constexpr int DET_THREADS = 256;                // scan block (4 waves)
+constexpr uint64_t KEY_SENTINEL = ~0ull;        // sorts after every real key
+
+// fp32 -> uint32 whose unsigned order is the DESCENDING float order (an ascending sort of the
+// keys then yields logit descending), and back
+__device__ __forceinline__ uint32_t desc_bits(float v) {
+  const uint32_t u = __float_as_uint(v);
+  return ~(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u));
+}
+__device__ __forceinline__ float desc_float(uint32_t k) {
+  k = ~k;
+  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
+}
+// scan key: class (8) | logit, descending (32) | anchor index in the image (24)
+__device__ __forceinline__ uint64_t make_key(int c, float v, int i) {
+  if (v == 0.f) v = 0.f;  // -0 and +0 are one score
+  return ((uint64_t)c << 56) | ((uint64_t)desc_bits(v) << 24) | (uint64_t)i;
+}
+
+// The scan block `bid` of a grid numbered (image, level, chunk): its image, its level, the
+// first pyramid row of its chunk, the chunk's rows and the image-flat index of the chunk's
+// first anchor.  nbi: blocks per image.
+struct ScanBlock {
+  int n, first;   // image; index of the image's first block
+  int64_t row0;   // first pyramid row
+  int nr;         // rows (<= DET_CH)
+  int abase;      // flat anchor index of (row0, a = 0) within the image
+};
+__device__ __forceinline__ ScanBlock scan_block(const edet_pyramid& p, int A, int nbi, int bid) {
+  ScanBlock b;
+  b.n = bid / nbi;
+  b.first = b.n * nbi;
+  int c = bid - b.first, ab = 0, s = 0;
+  for (; s < p.nseg - 1; ++s) {
+    const int hw = p.H[s] * p.W[s], nc = cdiv(hw, DET_CH);
+    if (c < nc) break;
+    c -= nc;
+    ab += hw * A;
+  }
+  const int hw = p.H[s] * p.W[s];
+  b.row0 = (int64_t)p.row_off[s] + (int64_t)b.n * hw + (int64_t)c * DET_CH;
+  b.nr = min(DET_CH, hw - c * DET_CH);
+  b.abase = ab + c * DET_CH * A;
+  return b;
+}
+
+// A block's chunk is the contiguous element span [e0, e1) of the logits buffer (its rows, up
+// to the last row's last used column).  It is read as "virtual vectors" of 16 bytes on the
+// buffer's 16-byte grid: vector v covers elements [ea + v * VE, ea + (v + 1) * VE) with ea the
+// grid point at or below e0.  Interior vectors are one aligned 16-byte load; the first and
+// the last may straddle the span's ends and are read element by element (the scalar prologue
+// and epilogue).  Vector order is element order, so it is flat candidate order.
+template <typename T>
+struct Span {
+  static constexpr int VE = 16 / (int)sizeof(T);
+  const T* cls;
+  int64_t e0, e1, ea, eb;  // eb: element offset of the chunk's first row (== e0)
+  int nv, ldc, anc, NC, A, abase;
+  float thr;
+
+  __device__ __forceinline__ Span(const T* cls_, const ScanBlock& b, int ldc_, int A_, int NC_, float thr_)
+      : cls(cls_), ldc(ldc_), anc(A_ * NC_), NC(NC_), A(A_), abase(b.abase), thr(thr_) {
+    e0 = eb = b.row0 * ldc;
+    e1 = (b.row0 + b.nr - 1) * ldc + anc;
+    const int mis = (int)(((uintptr_t)(cls + e0) & 15) / sizeof(T));
+    ea = e0 - mis;
+    nv = (int)((e1 - ea + VE - 1) / VE);
+  }
+  __device__ __forceinline__ bool full(int v) const {
+    const int64_t es = ea + (int64_t)v * VE;
+    return v < nv && es >= e0 && es + VE <= e1;
+  }
+  // the 16 bytes of an interior vector (issued ahead of their use); zeros otherwise
+  __device__ __forceinline__ uint4 fetch(int v) const {
+    return full(v) ? gld16(cls + ea + (int64_t)v * VE) : make_uint4(0u, 0u, 0u, 0u);
+  }
+  // class and image-flat anchor of span element `rel` (relative to eb); false for a pad
+  // column or the background class.  Only lanes that passed the compare get here.
+  __device__ __forceinline__ bool locate(int rel, int& c, int& i) const {
+    const int r = rel / ldc, col = rel - r * ldc;
+    const int a = col / NC;
+    c = col - a * NC;
+    i = abase + r * A + a;
+    return col < anc && c != 0;
+  }
+  // values of vector v and the mask of its candidates
+  __device__ __forceinline__ uint32_t eval(int v, uint4 raw, float* o) const {
+    const int64_t es = ea + (int64_t)v * VE;
+    uint32_t m = 0;
+    if (full(v)) {
+      if constexpr (sizeof(T) == 2) {
+        const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          o[2 * j] = __uint_as_float(w[j] << 16);
+          o[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+        }
+      } else {
+        o[0] = __uint_as_float(raw.x); o[1] = __uint_as_float(raw.y);
+        o[2] = __uint_as_float(raw.z); o[3] = __uint_as_float(raw.w);
+      }
+#pragma unroll
+      for (int j = 0; j < VE; ++j) m |= (uint32_t)(o[j] >= thr) << j;
+    } else if (v < nv) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const int64_t e = es + j;
+        const bool in = e >= e0 && e < e1;
+        o[j] = in ? to_f<T>(cls[in ? e : e0]) : 0.f;
+        m |= (uint32_t)(in && o[j] >= thr) << j;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) o[j] = 0.f;
+    }
+    if (m) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        int c, i;
+        if (((m >> j) & 1u) && !locate((int)(es + j - eb), c, i)) m &= ~(1u << j);
+      }
+    }
+    return m;
+  }
+};
+
+// Pass 1: counts[bid] = candidates in the block's chunk.
+template <typename T>
+__global__ __launch_bounds__(DET_THREADS) void k_cand_count(const T* cls, int ldc, edet_pyramid p, int A, int NC,
+                                                            int nbi, float thr, int32_t* counts) {
+  __shared__ int wsum[DET_THREADS / 64];
+  const ScanBlock b = scan_block(p, A, nbi, blockIdx.x);
+  const Span<T> sp(cls, b, ldc, A, NC, thr);
+  int cnt = 0;
+  uint4 raw = sp.fetch(threadIdx.x);
+  for (int v = threadIdx.x; v < sp.nv; v += DET_THREADS) {
+    const uint4 nxt = sp.fetch(v + DET_THREADS);
+    float o[Span<T>::VE];
+    cnt += __popc(sp.eval(v, raw, o));
+    raw = nxt;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) counts[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// Pass 2: the block's offset within its image is the sum of the counts of the image's blocks
+// before it (the block adds them itself); it then streams its chunk again and writes survivor
+// k of the image to cand[n][k] while k < cap.  The image's last block writes total / overflow.
+template <typename T>
+__global__ __launch_bounds__(DET_THREADS) void k_cand_write(const T* cls, int ldc, edet_pyramid p, int A, int NC,
+                                                            int nbi, float thr, const int32_t* counts, int cap,
+                                                            uint64_t* cand, int32_t* total, int32_t* overflow) {
+  constexpr int VE = Span<T>::VE, NW = DET_THREADS / 64;
+  __shared__ int wsum[2][NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ScanBlock b = scan_block(p, A, nbi, blockIdx.x);
+  int base = 0;
+  for (int j = b.first + tid; j < (int)blockIdx.x; j += DET_THREADS) base += counts[j];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) base += __shfl_xor(base, o, 64);
+  if (lane == 0) wsum[0][wave] = base;
+  __syncthreads();
+  base = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
+  __syncthreads();
+  const int mine = counts[blockIdx.x];
+  if ((int)blockIdx.x == b.first + nbi - 1 && tid == 0) {
+    total[b.n] = base + mine;
+    overflow[b.n] = (base + mine > cap) ? 1 : 0;
+  }
+  if (mine == 0 || base >= cap) return;  // block-uniform
+
+  const Span<T> sp(cls, b, ldc, A, NC, thr);
+  uint64_t* out = cand + (size_t)b.n * cap;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  int run = base;  // candidates of the image before this round, the same in every thread
+  uint4 raw = sp.fetch(tid);
+  for (int v0 = 0, r = 0; v0 < sp.nv && run < cap; v0 += DET_THREADS, r ^= 1) {
+    const int v = v0 + tid;
+    const uint4 nxt = sp.fetch(v + DET_THREADS);
+    float o[VE];
+    const uint32_t m = sp.eval(v, raw, o);
+    raw = nxt;
+    // lane offset: the candidates of the lower lanes' vectors (ballot + popcount per element
+    // slot), only in waves that hold a candidate at all
+    int loff = 0, wtot = 0;
+    if (__ballot(m != 0)) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const uint64_t bj = __ballot((m >> j) & 1u);
+        loff += __popcll(bj & lt);
+        wtot += __popcll(bj);
+      }
+    }
+    if (lane == 0) wsum[r][wave] = wtot;
+    __syncthreads();  // (one per round: the two wsum rows alternate)
+    int pos = run + loff;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const int t = wsum[r][w];
+      pos += (w < wave) ? t : 0;
+      run += t;
+    }
+    if (m) {
+      const int rel0 = (int)(sp.ea + (int64_t)v * VE - sp.eb);
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        if ((m >> j) & 1u) {
+          int c, i;
+          sp.locate(rel0 + j, c, i);
+          if (pos < cap) out[pos] = make_key(c, o[j], i);
+          ++pos;
+        }
+      }
+    }
+  }
+}
+
+// ascending bitonic sort of P (a power of two) keys in LDS by the whole block
+__device__ __forceinline__ void bitonic_sort(uint64_t* k, int P) {
+  for (int kk = 2; kk <= P; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const uint64_t a = k[i], b = k[l];
+        if ((a > b) == ((i & kk) == 0)) { k[i] = b; k[l] = a; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ float lane_bcast(float v, int src) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
+}
+
+// One 1024-thread block per image.  Dynamic LDS: keys[pcap] (8 B) then boxes[cap] (16 B), pcap
+// the power of two at or above cap.
+template <typename T>
+__global__ __launch_bounds__(1024) void k_nms_pc(const float* anchors, edet_pyramid p, int A, const T* box, int ldb,
+                                                 int NC, const uint64_t* cand, const int32_t* total, int cap,
+                                                 int pcap, int max_out, float iou_thr, int diou, float* out_boxes,
+                                                 int32_t* out_cls, float* out_scores, int32_t* out_count) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ int cstart[256], cend[256];
+  __shared__ int next_cls;
+  uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
+  float4* boxes = reinterpret_cast<float4*>(smem + (size_t)pcap * 8);
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int m = min(total[n], cap);
+  if (m == 0) {  // block-uniform
+    if (tid == 0) out_count[n] = 0;
+    return;
+  }
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int q = tid; q < P; q += blockDim.x) keys[q] = (q < m) ? cand[(size_t)n * cap + q] : KEY_SENTINEL;
+  if (tid < 256) { cstart[tid] = 0; cend[tid] = 0; }
+  if (tid == 0) next_cls = 1;
+  __syncthreads();
+  bitonic_sort(keys, P);  // class ascending, logit descending, anchor ascending
+
+  // boxes of the sorted candidates, and the class segments [cstart, cend)
+  for (int q = tid; q < m; q += blockDim.x) {
+    const uint64_t k = keys[q];
+    const int i = (int)(k & 0xffffffu), c = (int)(k >> 56);
+    int64_t row;
+    int a;
+    cand_locate(p, A, n, i, row, a);
+    float bx[4];
+    decode_one<T>(anchors + (size_t)i * 4, box + row * ldb + a * 4, bx);
+    boxes[q] = make_float4(bx[0], bx[1], bx[2], bx[3]);
+    if (q == 0 || (int)(keys[q - 1] >> 56) != c) cstart[c] = q;
+    if (q == m - 1 || (int)(keys[q + 1] >> 56) != c) cend[c] = q + 1;
+  }
+  __syncthreads();
+
+  // Greedy NMS, a wave per class.  The class's kept boxes are compacted to the front of its
+  // own segment of `boxes` (kept box k at s0 + k, never past the candidate being resolved, and
+  // every lane of the tile holds its own box in registers by then).  A candidate's key is
+  // rewritten as its output key (logit desc, anchor, class), or the sentinel when dropped.
+  for (;;) {
+    int c = 0;
+    if (lane == 0) c = atomicAdd(&next_cls, 1);  // which wave takes a class does not reach the result
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= NC) break;
+    const int s0 = cstart[c], s1 = cend[c];
+    int nk = 0;
+    for (int t0 = s0; t0 < s1; t0 += 64) {
+      const int q = t0 + lane;
+      const bool valid = q < s1;
+      const uint64_t key = valid ? keys[q] : KEY_SENTINEL;
+      const float4 bq = boxes[valid ? q : s0];
+      const float b[4] = {bq.x, bq.y, bq.z, bq.w};
+      bool alive = valid && nk < max_out, kept = false;
+      for (int k = 0; k < nk && alive; ++k) {  // against the boxes kept from earlier tiles
+        const float4 kq = boxes[s0 + k];
+        const float kb[4] = {kq.x, kq.y, kq.z, kq.w};
+        if ((diou ? diou_tf(kb, b) : iou_tf(kb, b)) >= iou_thr) alive = false;
+      }
+      uint64_t live = __ballot(alive);
+      while (live && nk < max_out) {  // the lowest live lane is kept, the lanes above test against it
+        const int l = __builtin_ctzll(live);
+        const float kb[4] = {lane_bcast(b[0], l), lane_bcast(b[1], l), lane_bcast(b[2], l), lane_bcast(b[3], l)};
+        if (lane == l) {
+          kept = true;
+          alive = false;
+          boxes[s0 + nk] = make_float4(kb[0], kb[1], kb[2], kb[3]);
+        }
+        ++nk;
+        if (alive && (diou ? diou_tf(kb, b) : iou_tf(kb, b)) >= iou_thr) alive = false;
+        live = __ballot(alive);
+      }
+      if (valid)
+        keys[q] = kept ? (((key >> 24) & 0xffffffffull) << 32) | ((key & 0xffffffull) << 8) | (key >> 56)
+                       : KEY_SENTINEL;
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // the next tile reads this tile's kept boxes
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+  __syncthreads();
+  bitonic_sort(keys, P);  // logit descending, anchor ascending, class ascending; dropped last
+
+  const int lim = min(max_out, m);
+  for (int k = tid; k < lim; k += blockDim.x) {
+    const uint64_t key = keys[k];
+    if (key == KEY_SENTINEL) continue;
+    if (k + 1 == lim || keys[k + 1] == KEY_SENTINEL) out_count[n] = k + 1;  // (m > 0: at least one is kept)
+    const int i = (int)((key >> 8) & 0xffffffu);
+    int64_t row;
+    int a;
+    cand_locate(p, A, n, i, row, a);
+    // the kept box again from its regression: the compaction above reused the LDS boxes
+    decode_one<T>(anchors + (size_t)i * 4, box + row * ldb + a * 4, out_boxes + ((size_t)n * max_out + k) * 4);
+    out_cls[(size_t)n * max_out + k] = (int)(key & 0xffu);
+    out_scores[(size_t)n * max_out + k] = 1.0f / (1.0f + expf(-desc_float((uint32_t)(key >> 32))));
+  }
+}
+
+}  // namespace edet
+
+using namespace edet;
+
+extern "C" {
+
+int edet_detect_per_class(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                          const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
+                          float logit_thr, int metric, void* scratch, float* out_boxes, int32_t* out_cls,
+                          float* out_scores, int32_t* out_count, int32_t* out_total, int32_t* out_overflow,
+                          edet_stream_t stream) {
+  EDET_REQUIRE(anchors && box && cls && p && scratch && out_boxes && out_cls && out_scores && out_count &&
+                   out_total && out_overflow,
+               "detect_per_class: null argument");
+  EDET_REQUIRE(dtype == EDET_F32 || dtype == EDET_BF16, "detect_per_class: unsupported dtype %d", dtype);
+  EDET_REQUIRE(NC >= 2 && NC <= 256, "detect_per_class: NC %d outside 2..256 (class 0 is background, 8 key bits)", NC);
+  EDET_REQUIRE(A > 0 && p->nseg >= 1 && p->nseg <= EDET_MAX_SEG, "detect_per_class: bad pyramid or A");
+  EDET_REQUIRE(max_candidates >= 1 && max_candidates <= EDET_DETECT_MAX_CANDIDATES,
+               "detect_per_class: max_candidates %d outside 1..%d", max_candidates, EDET_DETECT_MAX_CANDIDATES);
+  EDET_REQUIRE(max_out >= 1 && max_out <= max_candidates, "detect_per_class: max_out %d outside 1..max_candidates",
+               max_out);
+  EDET_REQUIRE(ldc >= A * NC, "detect_per_class: ldc %d < A*NC", ldc);
+  EDET_REQUIRE(ldb >= 4 * A, "detect_per_class: ldb %d < 4*A", ldb);
+  EDET_REQUIRE(metric == EDET_OVERLAP_IOU || metric == EDET_OVERLAP_DIOU, "detect_per_class: unknown metric %d",
+               metric);
+  EDET_REQUIRE(logit_thr == logit_thr, "detect_per_class: the logit threshold is NaN");
+  EDET_REQUIRE(((uintptr_t)scratch & 7) == 0, "detect_per_class: scratch not 8-byte aligned");
+  int64_t N = 0;
+  int nbi = 0;
+  for (int s = 0; s < p->nseg; ++s) {
+    N += (int64_t)p->H[s] * p->W[s] * A;
+    nbi += cdiv(p->H[s] * p->W[s], DET_CH);
+  }
+  EDET_REQUIRE(N < (1 << 24), "detect_per_class: %lld anchors per image, the key holds 24 bits", (long long)N);
+  EDET_REQUIRE((int64_t)DET_CH * ldc < (1 << 30) && (int64_t)p->batch * nbi < (1 << 30),
+               "detect_per_class: problem too large");
+  if (p->batch == 0 || N == 0) return EDET_OK;
+  uint64_t* cand = (uint64_t*)scratch;
+  int32_t* counts = (int32_t*)(cand + (size_t)p->batch * max_candidates);
+  int pcap = 2;  // (at least 16 bytes of keys: the boxes behind them stay 16-byte aligned)
+  while (pcap < max_candidates) pcap <<= 1;
+  const size_t lds = (size_t)pcap * 8 + (size_t)max_candidates * 16;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)(p->batch * nbi));
+  EDET_DTYPE_DISPATCH(dtype, T, {
+    if (lds > 48 * 1024) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nms_pc<T>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) {
+        set_error("detect_per_class: %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+        return EDET_EHIP;
+      }
+    }
+    EDET_LAUNCH(k_cand_count<T>, grid, dim3(DET_THREADS), 0, st, (const T*)cls, ldc, *p, A, NC, nbi, logit_thr, counts);
+    EDET_LAUNCH(k_cand_write<T>, grid, dim3(DET_THREADS), 0, st, (const T*)cls, ldc, *p, A, NC, nbi, logit_thr, counts,
+                max_candidates, cand, out_total, out_overflow);
+    EDET_LAUNCH(k_nms_pc<T>, dim3(p->batch), dim3(1024), lds, st, anchors, *p, A, (const T*)box, ldb, NC, cand,
+                out_total, max_candidates, pcap, max_out, iou_thr, metric == EDET_OVERLAP_DIOU ? 1 : 0, out_boxes,
+                out_cls, out_scores, out_count);
+    return check_launch("edet detect_per_class");
+  });
+}
+
+}  // extern "C"
