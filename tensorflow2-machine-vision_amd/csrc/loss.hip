@@ -151,7 +151,8 @@ __global__ __launch_bounds__(256) void k_loss(LossArgs g) {
         ld8(px, x);
         const int32_t* tr = g.cls_t + (size_t)m * g.A;
         const int a0 = (int)(((float)cv + 0.5f) * invNC);  // exact for cv < 2^20
-        const int ta = tr[a0], tb = (a0 + 1 < g.A) ? tr[a0 + 1] : -1;
+        // a0 >= A in a vector that lies wholly in the pad columns (ldc >= roundup8(A*NC) + 8)
+        const int ta = (a0 < g.A) ? tr[a0] : -1, tb = (a0 + 1 < g.A) ? tr[a0 + 1] : -1;
         const int p0 = (ta >= 0 && ta < g.NC) ? a0 * g.NC + ta : -1;
         const int p1 = (tb >= 0 && tb < g.NC) ? (a0 + 1) * g.NC + tb : -1;
 #pragma unroll
@@ -186,7 +187,8 @@ __global__ __launch_bounds__(256) void k_loss(LossArgs g) {
         // and, with NC >= 8, stay within two anchors whose targets are read once
         const int a0 = cv / g.NC;
         int a = a0, c = cv - a0 * g.NC;
-        const int ta = tr[a0], tb = (a0 + 1 < g.A) ? tr[a0 + 1] : -1;
+        // (a0 >= A in a vector that lies wholly in the pad columns)
+        const int ta = (a0 < g.A) ? tr[a0] : -1, tb = (a0 + 1 < g.A) ? tr[a0 + 1] : -1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int col = cv + j;
