@@ -473,6 +473,33 @@ int edet_detect_per_class(int dtype, const float* anchors, const void* box, int 
                           float* out_scores, int32_t* out_count, int32_t* out_total, int32_t* out_overflow,
                           edet_stream_t stream);
 
+/* edet_detect_per_class with a choice of the candidates that enter NMS when an image has more
+ * than max_candidates (total > max_candidates; out_overflow[n] = 1 either way).  select is
+ * inserted before scratch; every other argument is edet_detect_per_class's.
+ *
+ * EDET_SELECT_FIRST: exactly edet_detect_per_class (the first in ascending flat id), with its
+ * scratch size.
+ * EDET_SELECT_TOPK: the first max_candidates in the order (logit descending, flat id i*NC + c
+ * ascending): an exact top-K by score, ties at the boundary resolved by flat id.  -0 and +0
+ * are one score; a bf16 logit is its exact fp32 value.  With total <= max_candidates every
+ * candidate enters and every output equals EDET_SELECT_FIRST's bit for bit.  out_total, NMS,
+ * the output order and max_out are unchanged.  The selection is a radix select over integer
+ * histograms (3 digit passes for fp32, 2 for bf16, then a count and an ordered write): 8 launches
+ * for fp32 and 7 for bf16 in a fixed sequence, no allocation, no host sync, and no outcome
+ * depends on the order of atomic operations.
+ *
+ * scratch for EDET_SELECT_TOPK (8-byte aligned), with nbi = sum_l ceil(H_l*W_l /
+ * EDET_DETECT_CHUNK_ROWS): batch * (8*max_candidates + 12*nbi + 32 + 24576) bytes, laid out as
+ * keys [batch][max_candidates] (8 B) | block counts [batch*nbi] | better-than-threshold counts
+ * [batch*nbi] | equal-to-threshold counts [batch*nbi] | select state [batch][8] | digit
+ * histograms [batch][3][2048] (all int32). */
+enum { EDET_SELECT_FIRST = 0, EDET_SELECT_TOPK = 1 };
+int edet_detect_per_class_select(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                                 const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
+                                 float logit_thr, int metric, int select, void* scratch, float* out_boxes,
+                                 int32_t* out_cls, float* out_scores, int32_t* out_count, int32_t* out_total,
+                                 int32_t* out_overflow, edet_stream_t stream);
+
 /* ---- optimizer: L2 + clip_by_global_norm + SGD momentum + EMA, fused ----
  * scalars: [0] loss  [1] sum g^2  [2] sum w^2 (L2 params)  [3] gnorm  [4] lr  [5] npos
  *          [6] 1 when edet_opt_apply skipped a non-finite step (sched->skip_nonfinite), else 0

@@ -53,6 +53,15 @@ def stat_unfold(v):
     return out
 DETECT_MAX_CANDIDATES, DETECT_CHUNK_ROWS = 4096, 16  # EDET_DETECT_MAX_CANDIDATES, EDET_DETECT_CHUNK_ROWS
 OVERLAP = {"iou": 0, "diou": 1}  # EDET_OVERLAP_IOU, EDET_OVERLAP_DIOU
+SELECT = {"first": 0, "topk": 1}  # EDET_SELECT_FIRST, EDET_SELECT_TOPK
+
+
+def detect_scratch_bytes(batch: int, max_candidates: int, nbi: int, select: int = 0) -> int:
+    """Scratch of edet_detect_per_class[_select] (include/edet.h); nbi = blocks per image."""
+    per_image = 8 * max_candidates + 4 * nbi
+    if select == SELECT["topk"]:
+        per_image += 8 * nbi + 32 + 3 * 2048 * 4  # better / equal counts, select state, digit histograms
+    return batch * per_image
 ACT_NONE, ACT_SWISH = 0, 1
 MODE_SAME, MODE_UPSAMPLE, MODE_MAXPOOL = 0, 1, 2
 
@@ -187,6 +196,8 @@ SIGNATURES = {
     "edet_detect_nms": [c_int, P, P, c_int, PPyr, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P],
     "edet_detect_per_class": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float, c_float,
                               c_int, P, P, P, P, P, P, P, P],
+    "edet_detect_per_class_select": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float,
+                                     c_float, c_int, c_int, P, P, P, P, P, P, P, P],
     "edet_opt_norm": [P, P, c_int64, c_int64, PSched, P, P, P, P],
     "edet_opt_apply": [P, P, P, P, c_int64, c_int64, PSched, P, P, c_int, P, P, P],
     "edet_cast_f32": [c_int, P, P, c_int64, P],

@@ -209,7 +209,7 @@ class Anchors:
 
     def detect_per_class(self, outputs_boxes, outputs_classes, max_output_size: int = 100,
                          iou_threshold: float = 0.5, score_threshold: float = 0.05, metric: str = "iou",
-                         max_candidates: int = L.DETECT_MAX_CANDIDATES):
+                         max_candidates: int = L.DETECT_MAX_CANDIDATES, select: str = "first"):
         """Multi-label, per-class post-processing (include/edet.h, edet_detect_per_class): every
         (anchor, class >= 1) pair with sigmoid(logit) >= score_threshold is a candidate, greedy
         NMS (``metric`` "iou" or "diou") runs within each class, and the image's best
@@ -218,11 +218,16 @@ class Anchors:
         outputs_boxes / outputs_classes: the raw per-level regressions [B,H,W,A,4] and logits
         [B,H,W,A,NC] as returned by EfficientDetNet.call (boxes NOT decoded: only the
         candidates' are, inside the kernel).  At most max_candidates candidates per image enter
-        NMS, the first in flat (anchor, class) order.  Returns (boxes [B,max,4], class ids
+        NMS.  With more, ``select`` chooses them: "first" takes the first in flat (anchor, class)
+        order; "topk" (edet_detect_per_class_select) takes the best by (logit descending, flat id
+        anchor * NC + class ascending), an exact top-K whose boundary ties go to the lower flat
+        id.  Without overflow the two agree bit for bit.  Returns (boxes [B,max,4], class ids
         [B,max], scores [B,max], counts [B], total [B] candidates found, overflow [B] 1 where
         total > max_candidates); rows past counts[b] are unspecified."""
         if metric not in L.OVERLAP:
             raise ValueError(f"metric {metric!r}: expected one of {sorted(L.OVERLAP)}")
+        if select not in L.SELECT:
+            raise ValueError(f"select {select!r}: expected one of {sorted(L.SELECT)}")
         if not 0.0 <= score_threshold < 1.0:
             raise ValueError(f"score_threshold {score_threshold} outside [0, 1)")
         # the comparison runs in logit space: fp32(log(s / (1 - s))) from fp64
@@ -236,14 +241,19 @@ class Anchors:
         assert bdt == cdt, "regressions and logits must share the model dtype"
         dev = self.device
         nbi = sum(-(-h * w // L.DETECT_CHUNK_ROWS) for h, w in self.level_sizes)
-        scratch = torch.empty(B * (2 * max(max_candidates, 0) + nbi), dtype=torch.int32, device=dev)
+        nbytes = L.detect_scratch_bytes(B, max(max_candidates, 0), nbi, L.SELECT[select])
+        scratch = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
         ob = torch.empty((B, max_output_size, 4), dtype=torch.float32, device=dev)
         oc = torch.empty((B, max_output_size), dtype=torch.int32, device=dev)
         os_ = torch.empty((B, max_output_size), dtype=torch.float32, device=dev)
         cnt, total, over = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
-        L.call("edet_detect_per_class", cdt, vp(self.flat), bptr, bld, cptr, cld, pyr.c, A, NC, max_candidates,
-               max_output_size, float(iou_threshold), logit_thr, L.OVERLAP[metric], vp(scratch),
-               vp(ob), vp(oc), vp(os_), vp(cnt), vp(total), vp(over), stream())
+        head = (cdt, vp(self.flat), bptr, bld, cptr, cld, pyr.c, A, NC, max_candidates, max_output_size,
+                float(iou_threshold), logit_thr, L.OVERLAP[metric])
+        tail = (vp(scratch), vp(ob), vp(oc), vp(os_), vp(cnt), vp(total), vp(over), stream())
+        if select == "first":
+            L.call("edet_detect_per_class", *head, *tail)
+        else:
+            L.call("edet_detect_per_class_select", *head, L.SELECT[select], *tail)
         return ob, oc, os_, cnt, total, over
 
     def convert_outputs_one(self, batch_index: int, outputs_boxes, outputs_classes):

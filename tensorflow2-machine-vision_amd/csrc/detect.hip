@@ -6,12 +6,17 @@
 //                                 compaction: blocks own contiguous row chunks numbered in flat
 //                                 (image, level, row) order, pass 1 counts, pass 2 sums the counts
 //                                 of the blocks before it and writes its survivors in place
+//   k_sel_hist / k_sel_count /    EDET_SELECT_TOPK only, for images with more candidates than the
+//   k_sel_write                   cap: a most-significant-digit radix select of the cap-th best
+//                                 logit key over the same grid (one integer histogram per digit),
+//                                 then an ordered write of the candidates above the threshold key
+//                                 and of the first of those equal to it
 //   k_nms_pc                      one block per image: LDS bitonic sort by (class, logit desc,
 //                                 anchor), decode of the candidates' boxes only, wave-parallel
 //                                 greedy NMS per class out of LDS, final sort by score
 //
-// No floating-point atomics and no order-dependent integer atomics: the candidate list, and so
-// every output, is a function of the inputs alone.
+// No floating-point atomics and no order-dependent integer atomics (the histograms are integer
+// sums): the candidate list, and so every output, is a function of the inputs alone.
 #pragma clang fp contract(off)
 #include "boxes.hpp"
 
@@ -144,12 +149,22 @@ struct Span {
   }
 };
 
-// Pass 1: counts[bid] = candidates in the block's chunk.
-template <typename T>
+constexpr int SEL_BINS = 2048;   // bins of one digit's histogram (11 bits; the last fp32 digit uses 1024)
+constexpr int SEL_DIGITS = 3;    // histograms per image in scratch
+constexpr int SEL_STATE = 8;     // ints of select state per image: (prefix, rank) after each digit
+
+// Pass 1: counts[bid] = candidates in the block's chunk.  ZERO (the top-K path): an image's
+// first block also clears the image's digit histograms.
+template <typename T, bool ZERO = false>
 __global__ __launch_bounds__(DET_THREADS) void k_cand_count(const T* cls, int ldc, edet_pyramid p, int A, int NC,
-                                                            int nbi, float thr, int32_t* counts) {
+                                                            int nbi, float thr, int32_t* counts, int32_t* hist) {
   __shared__ int wsum[DET_THREADS / 64];
   const ScanBlock b = scan_block(p, A, nbi, blockIdx.x);
+  if constexpr (ZERO) {
+    if ((int)blockIdx.x == b.first)
+      for (int q = threadIdx.x; q < SEL_DIGITS * SEL_BINS; q += DET_THREADS)
+        hist[(size_t)b.n * SEL_DIGITS * SEL_BINS + q] = 0;
+  }
   const Span<T> sp(cls, b, ldc, A, NC, thr);
   int cnt = 0;
   uint4 raw = sp.fetch(threadIdx.x);
@@ -232,6 +247,254 @@ __global__ __launch_bounds__(DET_THREADS) void k_cand_write(const T* cls, int ld
           sp.locate(rel0 + j, c, i);
           if (pos < cap) out[pos] = make_key(c, o[j], i);
           ++pos;
+        }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------- exact top-K selection
+// An image with total > cap candidates keeps the first cap in (logit descending, flat id
+// ascending) order.  With k = sel_key(logit) that is: every candidate whose key is below the
+// cap-th smallest key T, and the first need_eq = cap - #{k < T} candidates with k == T in flat
+// order.  T is found digit by digit from the top (11 + 11 + 10 bits).  The pass of digit d
+// histograms that digit over the candidates whose higher digits equal the prefix of T known
+// so far; the next launch finds the bin in which the cumulative count reaches the remaining
+// rank.  A bf16 logit's low 10 key bits follow from its sign (the key's top bit), so two digits
+// order bf16 keys completely: the select then works on key >> 10.
+template <typename T>
+struct Sel {
+  static constexpr int ND = sizeof(T) == 2 ? 2 : 3;  // digit passes
+  static constexpr int KS = sizeof(T) == 2 ? 10 : 0;  // the select compares key >> KS
+};
+__device__ __forceinline__ int sel_shift(int d) { return d == 0 ? 21 : (d == 1 ? 10 : 0); }
+__device__ __forceinline__ int sel_width(int d) { return d == 2 ? 10 : 11; }
+__device__ __forceinline__ uint32_t sel_key(float v) {
+  if (v == 0.f) v = 0.f;  // -0 and +0 are one score (make_key)
+  return desc_bits(v);
+}
+
+// Resolve digit d of the image's threshold key: the bin of the digit's finished histogram gh
+// in which the running count first reaches `rank` (1-based, among the candidates under
+// `prefix`).  On return prefix has the digit appended and rank counts within that bin.  Every
+// block computes this for itself; the image's first block records it in st for the next launch.
+// lh (SEL_BINS ints) is staging space and is free again afterwards.
+__device__ __forceinline__ void sel_resolve(const int32_t* gh, int d, int* lh, int* wsum, int* res, bool record,
+                                            int32_t* st, uint32_t& prefix, int& rank) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int q = tid; q < SEL_BINS; q += DET_THREADS) lh[q] = gh[q];
+  if (tid == 0) { res[0] = 0; res[1] = 1; }
+  __syncthreads();
+  constexpr int PER = SEL_BINS / DET_THREADS;  // consecutive bins per thread
+  int s = 0;
+#pragma unroll
+  for (int j = 0; j < PER; ++j) s += lh[tid * PER + j];
+  int inc = s;  // inclusive scan over the block, in bin order
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(inc, o, 64);
+    inc += (lane >= o) ? t : 0;
+  }
+  if (lane == 63) wsum[wave] = inc;
+  __syncthreads();
+  int exc = inc - s;
+#pragma unroll
+  for (int w = 0; w < DET_THREADS / 64; ++w) exc += (w < wave) ? wsum[w] : 0;
+  if (exc < rank && rank <= exc + s) {  // one thread: the histogram holds at least `rank`
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+      const int c = lh[tid * PER + j];
+      if (exc < rank && rank <= exc + c) { res[0] = tid * PER + j; res[1] = rank - exc; }
+      exc += c;
+    }
+  }
+  __syncthreads();
+  prefix = (prefix << sel_width(d)) | (uint32_t)res[0];
+  rank = res[1];
+  if (record && tid == 0) { st[2 * d] = (int32_t)prefix; st[2 * d + 1] = rank; }
+  __syncthreads();  // lh, wsum and res are reused
+}
+
+// Digit pass d of an overflowing image: hist[n][d][bin] += the block's candidates under the
+// prefix (integer adds, order-free).  Blocks of an image within the cap leave at once.
+template <typename T>
+__global__ __launch_bounds__(DET_THREADS) void k_sel_hist(const T* cls, int ldc, edet_pyramid p, int A, int NC,
+                                                          int nbi, float thr, int cap, int d, const int32_t* total,
+                                                          int32_t* state, int32_t* hist) {
+  __shared__ int lh[SEL_BINS];
+  __shared__ int wsum[DET_THREADS / 64];
+  __shared__ int res[2];
+  const ScanBlock b = scan_block(p, A, nbi, blockIdx.x);
+  if (total[b.n] <= cap) return;  // block-uniform
+  int32_t* st = state + (size_t)b.n * SEL_STATE;
+  int32_t* gh = hist + (size_t)b.n * SEL_DIGITS * SEL_BINS;
+  uint32_t prefix = 0;
+  int rank = cap;
+  if (d > 0) {
+    if (d > 1) { prefix = (uint32_t)st[2 * (d - 2)]; rank = st[2 * (d - 2) + 1]; }
+    sel_resolve(gh + (d - 1) * SEL_BINS, d - 1, lh, wsum, res, (int)blockIdx.x == b.first, st, prefix, rank);
+  }
+  for (int q = threadIdx.x; q < SEL_BINS; q += DET_THREADS) lh[q] = 0;
+  __syncthreads();
+  const int sh = sel_shift(d), shp = d > 0 ? sel_shift(d - 1) : 0;
+  const uint32_t mask = (1u << sel_width(d)) - 1u;
+  const Span<T> sp(cls, b, ldc, A, NC, thr);
+  uint4 raw = sp.fetch(threadIdx.x);
+  for (int v = threadIdx.x; v < sp.nv; v += DET_THREADS) {
+    const uint4 nxt = sp.fetch(v + DET_THREADS);
+    float o[Span<T>::VE];
+    const uint32_t m = sp.eval(v, raw, o);
+    raw = nxt;
+    if (m) {
+#pragma unroll
+      for (int j = 0; j < Span<T>::VE; ++j) {
+        const uint32_t k = sel_key(o[j]);
+        if (((m >> j) & 1u) && (d == 0 || (k >> shp) == prefix)) atomicAdd(&lh[(k >> sh) & mask], 1);
+      }
+    }
+  }
+  __syncthreads();
+  for (int q = threadIdx.x; q < SEL_BINS; q += DET_THREADS) {
+    const int c = lh[q];
+    if (c) atomicAdd(&gh[d * SEL_BINS + q], c);
+  }
+}
+
+// After the last digit: the threshold key T (as key >> KS) and need_eq are known.  Per block,
+// cgt[bid] / ceq[bid] = its candidates better than / equal to T.
+template <typename T>
+__global__ __launch_bounds__(DET_THREADS) void k_sel_count(const T* cls, int ldc, edet_pyramid p, int A, int NC,
+                                                           int nbi, float thr, int cap, const int32_t* total,
+                                                           int32_t* state, const int32_t* hist, int32_t* cgt,
+                                                           int32_t* ceq) {
+  constexpr int ND = Sel<T>::ND, KS = Sel<T>::KS;
+  __shared__ int lh[SEL_BINS];
+  __shared__ int wsum[2 * (DET_THREADS / 64)];
+  __shared__ int res[2];
+  const ScanBlock b = scan_block(p, A, nbi, blockIdx.x);
+  if (total[b.n] <= cap) return;  // block-uniform
+  int32_t* st = state + (size_t)b.n * SEL_STATE;
+  uint32_t tk = (uint32_t)st[2 * (ND - 2)];
+  int need = st[2 * (ND - 2) + 1];
+  sel_resolve(hist + ((size_t)b.n * SEL_DIGITS + (ND - 1)) * SEL_BINS, ND - 1, lh, wsum, res,
+              (int)blockIdx.x == b.first, st, tk, need);
+  const Span<T> sp(cls, b, ldc, A, NC, thr);
+  int ngt = 0, neq = 0;
+  uint4 raw = sp.fetch(threadIdx.x);
+  for (int v = threadIdx.x; v < sp.nv; v += DET_THREADS) {
+    const uint4 nxt = sp.fetch(v + DET_THREADS);
+    float o[Span<T>::VE];
+    const uint32_t m = sp.eval(v, raw, o);
+    raw = nxt;
+    if (m) {
+#pragma unroll
+      for (int j = 0; j < Span<T>::VE; ++j) {
+        const uint32_t k = sel_key(o[j]) >> KS;
+        const bool c = (m >> j) & 1u;
+        ngt += (c && k < tk) ? 1 : 0;
+        neq += (c && k == tk) ? 1 : 0;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    ngt += __shfl_xor(ngt, o, 64);
+    neq += __shfl_xor(neq, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = ngt; wsum[4 + (threadIdx.x >> 6)] = neq; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    cgt[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    ceq[blockIdx.x] = (wsum[4] + wsum[5]) + (wsum[6] + wsum[7]);
+  }
+}
+
+// The ordered write of an overflowing image, over the first-in-flat-order keys k_cand_write
+// left there: candidate g of those better than T goes to cand[n][g], candidate e < need_eq of
+// those equal to T to cand[n][cap - need_eq + e]; g and e count in flat order (the block sums
+// its predecessors' counts itself, lanes by ballot + popcount, waves through two alternating
+// LDS rows as in k_cand_write).
+template <typename T>
+__global__ __launch_bounds__(DET_THREADS) void k_sel_write(const T* cls, int ldc, edet_pyramid p, int A, int NC,
+                                                           int nbi, float thr, int cap, const int32_t* total,
+                                                           const int32_t* state, const int32_t* cgt,
+                                                           const int32_t* ceq, uint64_t* cand) {
+  constexpr int VE = Span<T>::VE, NW = DET_THREADS / 64, ND = Sel<T>::ND, KS = Sel<T>::KS;
+  __shared__ int wsum[2][2 * NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const ScanBlock b = scan_block(p, A, nbi, blockIdx.x);
+  if (total[b.n] <= cap) return;  // block-uniform
+  const uint32_t tk = (uint32_t)state[(size_t)b.n * SEL_STATE + 2 * (ND - 1)];
+  const int need = state[(size_t)b.n * SEL_STATE + 2 * (ND - 1) + 1];
+  const int first_eq = cap - need;  // == the image's candidates better than T
+  int bg = 0, be = 0;
+  for (int j = b.first + tid; j < (int)blockIdx.x; j += DET_THREADS) { bg += cgt[j]; be += ceq[j]; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    bg += __shfl_xor(bg, o, 64);
+    be += __shfl_xor(be, o, 64);
+  }
+  if (lane == 0) { wsum[0][wave] = bg; wsum[0][NW + wave] = be; }
+  __syncthreads();
+  bg = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
+  be = (wsum[0][4] + wsum[0][5]) + (wsum[0][6] + wsum[0][7]);
+  __syncthreads();
+  if (cgt[blockIdx.x] == 0 && (ceq[blockIdx.x] == 0 || be >= need)) return;  // block-uniform
+
+  const Span<T> sp(cls, b, ldc, A, NC, thr);
+  uint64_t* out = cand + (size_t)b.n * cap;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  int rg = bg, re = be;  // candidates of the two kinds before this round, the same in every thread
+  uint4 raw = sp.fetch(tid);
+  for (int v0 = 0, r = 0; v0 < sp.nv; v0 += DET_THREADS, r ^= 1) {
+    const int v = v0 + tid;
+    const uint4 nxt = sp.fetch(v + DET_THREADS);
+    float o[VE];
+    const uint32_t m = sp.eval(v, raw, o);
+    raw = nxt;
+    uint32_t mg = 0, me = 0;
+    if (m) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const uint32_t k = sel_key(o[j]) >> KS;
+        mg |= (uint32_t)(((m >> j) & 1u) && k < tk) << j;
+        me |= (uint32_t)(((m >> j) & 1u) && k == tk) << j;
+      }
+    }
+    int og = 0, oe = 0, wg = 0, we = 0;
+    if (__ballot((mg | me) != 0)) {
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const uint64_t gj = __ballot((mg >> j) & 1u), ej = __ballot((me >> j) & 1u);
+        og += __popcll(gj & lt);
+        wg += __popcll(gj);
+        oe += __popcll(ej & lt);
+        we += __popcll(ej);
+      }
+    }
+    if (lane == 0) { wsum[r][wave] = wg; wsum[r][NW + wave] = we; }
+    __syncthreads();  // (one per round: the two wsum rows alternate)
+    int pg = rg + og, pe = re + oe;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const int tg = wsum[r][w], te = wsum[r][NW + w];
+      pg += (w < wave) ? tg : 0;
+      pe += (w < wave) ? te : 0;
+      rg += tg;
+      re += te;
+    }
+    if (mg | me) {
+      const int rel0 = (int)(sp.ea + (int64_t)v * VE - sp.eb);
+#pragma unroll
+      for (int j = 0; j < VE; ++j) {
+        const bool g = (mg >> j) & 1u, e = (me >> j) & 1u;
+        if (g || e) {
+          int c, i;
+          sp.locate(rel0 + j, c, i);
+          const int pos = g ? pg : ((pe < need) ? first_eq + pe : -1);
+          if ((unsigned)pos < (unsigned)cap) out[pos] = make_key(c, o[j], i);  // (never past the image's slots)
+          pg += g ? 1 : 0;
+          pe += e ? 1 : 0;
         }
       }
     }
@@ -363,13 +626,12 @@ __global__ __launch_bounds__(1024) void k_nms_pc(const float* anchors, edet_pyra
 
 using namespace edet;
 
-extern "C" {
-
-int edet_detect_per_class(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
-                          const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
-                          float logit_thr, int metric, void* scratch, float* out_boxes, int32_t* out_cls,
-                          float* out_scores, int32_t* out_count, int32_t* out_total, int32_t* out_overflow,
-                          edet_stream_t stream) {
+// both entry points; select is validated by the caller
+static int detect_per_class_run(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                                const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
+                                float logit_thr, int metric, int select, void* scratch, float* out_boxes,
+                                int32_t* out_cls, float* out_scores, int32_t* out_count, int32_t* out_total,
+                                int32_t* out_overflow, edet_stream_t stream) {
   EDET_REQUIRE(anchors && box && cls && p && scratch && out_boxes && out_cls && out_scores && out_count &&
                    out_total && out_overflow,
                "detect_per_class: null argument");
@@ -398,6 +660,13 @@ int edet_detect_per_class(int dtype, const float* anchors, const void* box, int 
   if (p->batch == 0 || N == 0) return EDET_OK;
   uint64_t* cand = (uint64_t*)scratch;
   int32_t* counts = (int32_t*)(cand + (size_t)p->batch * max_candidates);
+  // EDET_SELECT_TOPK: per-block better / equal counts, per-image select state and histograms
+  const size_t nblk = (size_t)p->batch * nbi;
+  int32_t* cgt = counts + nblk;
+  int32_t* ceq = cgt + nblk;
+  int32_t* state = ceq + nblk;
+  int32_t* hist = state + (size_t)p->batch * SEL_STATE;
+  const int cap = max_candidates;
   int pcap = 2;  // (at least 16 bytes of keys: the boxes behind them stay 16-byte aligned)
   while (pcap < max_candidates) pcap <<= 1;
   const size_t lds = (size_t)pcap * 8 + (size_t)max_candidates * 16;
@@ -412,14 +681,53 @@ int edet_detect_per_class(int dtype, const float* anchors, const void* box, int 
         return EDET_EHIP;
       }
     }
-    EDET_LAUNCH(k_cand_count<T>, grid, dim3(DET_THREADS), 0, st, (const T*)cls, ldc, *p, A, NC, nbi, logit_thr, counts);
-    EDET_LAUNCH(k_cand_write<T>, grid, dim3(DET_THREADS), 0, st, (const T*)cls, ldc, *p, A, NC, nbi, logit_thr, counts,
+    const T* lg = (const T*)cls;
+    if (select == EDET_SELECT_TOPK)
+      EDET_LAUNCH((k_cand_count<T, true>), grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, counts,
+                  hist);
+    else
+      EDET_LAUNCH(k_cand_count<T>, grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, counts,
+                  (int32_t*)nullptr);
+    EDET_LAUNCH(k_cand_write<T>, grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, counts,
                 max_candidates, cand, out_total, out_overflow);
+    if (select == EDET_SELECT_TOPK) {  // (blocks of an image with total <= cap return at once)
+      for (int d = 0; d < Sel<T>::ND; ++d)
+        EDET_LAUNCH(k_sel_hist<T>, grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, cap, d,
+                    out_total, state, hist);
+      EDET_LAUNCH(k_sel_count<T>, grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, cap, out_total,
+                  state, hist, cgt, ceq);
+      EDET_LAUNCH(k_sel_write<T>, grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, cap, out_total,
+                  state, cgt, ceq, cand);
+    }
     EDET_LAUNCH(k_nms_pc<T>, dim3(p->batch), dim3(1024), lds, st, anchors, *p, A, (const T*)box, ldb, NC, cand,
                 out_total, max_candidates, pcap, max_out, iou_thr, metric == EDET_OVERLAP_DIOU ? 1 : 0, out_boxes,
                 out_cls, out_scores, out_count);
     return check_launch("edet detect_per_class");
   });
+}
+
+extern "C" {
+
+int edet_detect_per_class(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                          const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
+                          float logit_thr, int metric, void* scratch, float* out_boxes, int32_t* out_cls,
+                          float* out_scores, int32_t* out_count, int32_t* out_total, int32_t* out_overflow,
+                          edet_stream_t stream) {
+  return detect_per_class_run(dtype, anchors, box, ldb, cls, ldc, p, A, NC, max_candidates, max_out, iou_thr,
+                              logit_thr, metric, EDET_SELECT_FIRST, scratch, out_boxes, out_cls, out_scores, out_count,
+                              out_total, out_overflow, stream);
+}
+
+int edet_detect_per_class_select(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                                 const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
+                                 float logit_thr, int metric, int select, void* scratch, float* out_boxes,
+                                 int32_t* out_cls, float* out_scores, int32_t* out_count, int32_t* out_total,
+                                 int32_t* out_overflow, edet_stream_t stream) {
+  EDET_REQUIRE(select == EDET_SELECT_FIRST || select == EDET_SELECT_TOPK,
+               "detect_per_class: select %d is neither EDET_SELECT_FIRST nor EDET_SELECT_TOPK", select);
+  return detect_per_class_run(dtype, anchors, box, ldb, cls, ldc, p, A, NC, max_candidates, max_out, iou_thr,
+                              logit_thr, metric, select, scratch, out_boxes, out_cls, out_scores, out_count, out_total,
+                              out_overflow, stream);
 }
 
 }  // extern "C"
