@@ -500,6 +500,37 @@ int edet_detect_per_class_select(int dtype, const float* anchors, const void* bo
                                  int32_t* out_cls, float* out_scores, int32_t* out_count, int32_t* out_total,
                                  int32_t* out_overflow, edet_stream_t stream);
 
+/* edet_detect_per_class_select with per-class Gaussian Soft-NMS, the published evaluation's
+ * default, in place of the hard IoU threshold.  The arguments are edet_detect_per_class_select's
+ * without iou_thr and with sigma and min_score after select; metric must be EDET_OVERLAP_IOU.
+ * Candidates, the cap, select, out_total, out_overflow and scratch are exactly as there.
+ *
+ * For each class c >= 1 of an image independently, over the candidates that enter:
+ *   1. s_j = 1 / (1 + exp(-logit_j)) in fp64; boxes are the fp32 decoded boxes widened to fp64.
+ *   2. While the class has live candidates and fewer than max_out picks: pick the live candidate
+ *      with the largest s (on exactly equal s the lower anchor index), emit (anchor, class, s)
+ *      and retire it; for every other live j, s_j = s_j * exp(-(ov * ov) / sigma) with ov the
+ *      IoU of the two boxes (the op order and the union == 0 -> 0 rule of edet_detect_nms's
+ *      IoU, in fp64 without contraction); then j is dropped if s_j < min_score.
+ *   3. Every emitted s is rounded to fp32 once.
+ * Output: of an image's emissions the first max_out by (fp32 score descending, anchor index
+ * ascending, class ascending), in the layout of edet_detect_per_class; out_scores holds the
+ * decayed scores.
+ *
+ * min_score (0 <= min_score < 1) is compared in score space and is normally the score threshold
+ * whose logit is logit_thr; with 0 nothing is dropped and a class stops at max_out picks.
+ * sigma > 0 and finite (the published default is 0.5).  Overlap, decay and the running scores
+ * are fp64 on the device: against an fp64 evaluation of the above only exp differs, by a few
+ * ulp per decay, so every choice agrees unless two quantities lie within ~1e-13 relative of
+ * each other.  One block per image holds 8 B key + 16 B box + 8 B score per candidate in LDS:
+ * 128 KiB at EDET_DETECT_MAX_CANDIDATES.  Same launches as edet_detect_per_class_select but
+ * for the last; no outcome depends on the order of atomic operations. */
+int edet_detect_per_class_soft(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                               const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float logit_thr,
+                               int metric, int select, double sigma, double min_score, void* scratch,
+                               float* out_boxes, int32_t* out_cls, float* out_scores, int32_t* out_count,
+                               int32_t* out_total, int32_t* out_overflow, edet_stream_t stream);
+
 /* ---- optimizer: L2 + clip_by_global_norm + SGD momentum + EMA, fused ----
  * scalars: [0] loss  [1] sum g^2  [2] sum w^2 (L2 params)  [3] gnorm  [4] lr  [5] npos
  *          [6] 1 when edet_opt_apply skipped a non-finite step (sched->skip_nonfinite), else 0

@@ -12,7 +12,7 @@ import os
 # libedet.so links libamdhip64.so.7; load torch first so the process has ONE HIP runtime
 # (torch's) and libedet binds to it instead of bringing up a second one.
 import torch  # noqa: F401
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 MAX_SEG = 5
 ABI_VERSION = 10  # must equal edet_abi_version() of the loaded library (struct layouts)
@@ -198,6 +198,8 @@ SIGNATURES = {
                               c_int, P, P, P, P, P, P, P, P],
     "edet_detect_per_class_select": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float,
                                      c_float, c_int, c_int, P, P, P, P, P, P, P, P],
+    "edet_detect_per_class_soft": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float, c_int,
+                                   c_int, c_double, c_double, P, P, P, P, P, P, P, P],
     "edet_opt_norm": [P, P, c_int64, c_int64, PSched, P, P, P, P],
     "edet_opt_apply": [P, P, P, P, c_int64, c_int64, PSched, P, P, c_int, P, P, P],
     "edet_cast_f32": [c_int, P, P, c_int64, P],

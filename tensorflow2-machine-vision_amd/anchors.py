@@ -209,7 +209,8 @@ class Anchors:
 
     def detect_per_class(self, outputs_boxes, outputs_classes, max_output_size: int = 100,
                          iou_threshold: float = 0.5, score_threshold: float = 0.05, metric: str = "iou",
-                         max_candidates: int = L.DETECT_MAX_CANDIDATES, select: str = "first"):
+                         max_candidates: int = L.DETECT_MAX_CANDIDATES, select: str = "first",
+                         nms: str = "hard", sigma: float = 0.5):
         """Multi-label, per-class post-processing (include/edet.h, edet_detect_per_class): every
         (anchor, class >= 1) pair with sigmoid(logit) >= score_threshold is a candidate, greedy
         NMS (``metric`` "iou" or "diou") runs within each class, and the image's best
@@ -221,9 +222,28 @@ class Anchors:
         NMS.  With more, ``select`` chooses them: "first" takes the first in flat (anchor, class)
         order; "topk" (edet_detect_per_class_select) takes the best by (logit descending, flat id
         anchor * NC + class ascending), an exact top-K whose boundary ties go to the lower flat
-        id.  Without overflow the two agree bit for bit.  Returns (boxes [B,max,4], class ids
-        [B,max], scores [B,max], counts [B], total [B] candidates found, overflow [B] 1 where
-        total > max_candidates); rows past counts[b] are unspecified."""
+        id.  Without overflow the two agree bit for bit.
+
+        ``nms="soft"`` (edet_detect_per_class_soft) replaces the hard threshold by the published
+        evaluation's per-class Gaussian Soft-NMS, over the same candidates; iou_threshold has no
+        role and metric must be "iou".  Each candidate starts at s = sigmoid(logit) in fp64.
+        While a class has live candidates and fewer than max_output_size picks, the live
+        candidate with the largest s is picked (on exactly equal s the lower anchor), emitted
+        with that s and retired; every other live s_j becomes s_j * exp(-iou^2 / ``sigma``)
+        (fp64, the IoU of the fp32 decoded boxes) and j is dropped once s_j < score_threshold,
+        compared in score space (with 0 nothing is dropped).  The emitted scores are rounded to
+        fp32 once; the image's best max_output_size emissions by (score desc, anchor, class) are
+        returned, and the scores are the decayed ones.
+
+        Returns (boxes [B,max,4], class ids [B,max], scores [B,max], counts [B], total [B]
+        candidates found, overflow [B] 1 where total > max_candidates); rows past counts[b] are
+        unspecified."""
+        if nms not in ("hard", "soft"):
+            raise ValueError(f"nms {nms!r}: expected 'hard' or 'soft'")
+        if nms == "soft" and metric != "iou":
+            raise ValueError(f"nms='soft' decays by the IoU: metric {metric!r} is not supported")
+        if not (sigma > 0.0 and np.isfinite(sigma)):
+            raise ValueError(f"sigma {sigma} is not positive and finite")
         if metric not in L.OVERLAP:
             raise ValueError(f"metric {metric!r}: expected one of {sorted(L.OVERLAP)}")
         if select not in L.SELECT:
@@ -250,7 +270,10 @@ class Anchors:
         head = (cdt, vp(self.flat), bptr, bld, cptr, cld, pyr.c, A, NC, max_candidates, max_output_size,
                 float(iou_threshold), logit_thr, L.OVERLAP[metric])
         tail = (vp(scratch), vp(ob), vp(oc), vp(os_), vp(cnt), vp(total), vp(over), stream())
-        if select == "first":
+        if nms == "soft":
+            L.call("edet_detect_per_class_soft", *head[:11], logit_thr, L.OVERLAP[metric], L.SELECT[select],
+                   float(sigma), float(score_threshold), *tail)
+        elif select == "first":
             L.call("edet_detect_per_class", *head, *tail)
         else:
             L.call("edet_detect_per_class_select", *head, L.SELECT[select], *tail)

@@ -22,6 +22,20 @@ __device__ __forceinline__ float iou_tf(const float* b1, const float* b2) {
   return (uni == 0.f) ? 0.f : inter / uni;  // divide_no_nan
 }
 
+// iou_tf in fp64, the same op order and the same uni == 0 -> 0 rule (Soft-NMS, detect.hip)
+__device__ __forceinline__ double iou_tf64(const double* b1, const double* b2) {
+  const double zero = 0.0;
+  const double b1_w = fmax(zero, b1[3] - b1[1]), b1_h = fmax(zero, b1[2] - b1[0]);
+  const double b2_w = fmax(zero, b2[3] - b2[1]), b2_h = fmax(zero, b2[2] - b2[0]);
+  const double a1 = b1_w * b1_h, a2 = b2_w * b2_h;
+  const double iy1 = fmax(b1[0], b2[0]), ix1 = fmax(b1[1], b2[1]);
+  const double iy2 = fmin(b1[2], b2[2]), ix2 = fmin(b1[3], b2[3]);
+  const double iw = fmax(zero, ix2 - ix1), ih = fmax(zero, iy2 - iy1);
+  const double inter = iw * ih;
+  const double uni = (a1 + a2) - inter;
+  return (uni == 0.0) ? 0.0 : inter / uni;  // divide_no_nan
+}
+
 // DIoU of b1 (the kept box) and b2 in get_iou's op order: iou - |c2 - c1|^2 / diag^2 with
 // the norms taken as sqrt(sum of squares) and squared again, divide_no_nan for both ratios
 __device__ __forceinline__ float diou_tf(const float* b1, const float* b2) {

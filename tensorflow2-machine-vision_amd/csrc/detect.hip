@@ -14,10 +14,16 @@
 //   k_nms_pc                      one block per image: LDS bitonic sort by (class, logit desc,
 //                                 anchor), decode of the candidates' boxes only, wave-parallel
 //                                 greedy NMS per class out of LDS, final sort by score
+//   k_softnms_pc                  edet_detect_per_class_soft, in place of k_nms_pc: the same sort
+//                                 and decode, then per-class Gaussian Soft-NMS in fp64, one pass
+//                                 over a class's live candidates per pick (decay, drop, arg-max,
+//                                 in-place compaction), small classes a wave each and large ones
+//                                 by the whole block (its section below)
 //
 // No floating-point atomics and no order-dependent integer atomics (the histograms are integer
 // sums): the candidate list, and so every output, is a function of the inputs alone.
 #pragma clang fp contract(off)
+#include <float.h>
 #include "boxes.hpp"
 
 namespace edet {
@@ -519,6 +525,63 @@ __device__ __forceinline__ float lane_bcast(float v, int src) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
 }
 
+// The start of both per-image kernels, by the whole block: the image's m candidate keys into
+// LDS (padded to the power of two P, which is returned), sorted by (class, logit descending,
+// anchor), the boxes of the sorted candidates and the class segments [cstart, cend).
+template <typename T>
+__device__ __forceinline__ int sort_candidates(const float* anchors, const edet_pyramid& p, int A, const T* box,
+                                               int ldb, const uint64_t* cand, int n, int m, uint64_t* keys,
+                                               float4* boxes, int* cstart, int* cend) {
+  const int tid = threadIdx.x;
+  int P = 1;
+  while (P < m) P <<= 1;
+  for (int q = tid; q < P; q += blockDim.x) keys[q] = (q < m) ? cand[q] : KEY_SENTINEL;
+  if (tid < 256) { cstart[tid] = 0; cend[tid] = 0; }
+  __syncthreads();
+  bitonic_sort(keys, P);  // class ascending, logit descending, anchor ascending
+
+  // boxes of the sorted candidates, and the class segments [cstart, cend)
+  for (int q = tid; q < m; q += blockDim.x) {
+    const uint64_t k = keys[q];
+    const int i = (int)(k & 0xffffffu), c = (int)(k >> 56);
+    int64_t row;
+    int a;
+    cand_locate(p, A, n, i, row, a);
+    float bx[4];
+    decode_one<T>(anchors + (size_t)i * 4, box + row * ldb + a * 4, bx);
+    boxes[q] = make_float4(bx[0], bx[1], bx[2], bx[3]);
+    if (q == 0 || (int)(keys[q - 1] >> 56) != c) cstart[c] = q;
+    if (q == m - 1 || (int)(keys[q + 1] >> 56) != c) cend[c] = q + 1;
+  }
+  __syncthreads();
+  return P;
+}
+
+// The end of both: keys holds the output keys (score or logit descending (32) | anchor (24) |
+// class (8)) sorted ascending, dropped candidates as the sentinel behind them.  Thread k writes
+// output k, its box decoded again from its regression (the LDS copy was reused).  SOFT: the
+// key's float is the score already; else it is the logit.
+template <typename T, bool SOFT>
+__device__ __forceinline__ void write_detections(const float* anchors, const edet_pyramid& p, int A, const T* box,
+                                                 int ldb, const uint64_t* keys, int n, int m, int max_out,
+                                                 float* out_boxes, int32_t* out_cls, float* out_scores,
+                                                 int32_t* out_count) {
+  const int lim = min(max_out, m);
+  for (int k = threadIdx.x; k < lim; k += blockDim.x) {
+    const uint64_t key = keys[k];
+    if (key == KEY_SENTINEL) continue;
+    if (k + 1 == lim || keys[k + 1] == KEY_SENTINEL) out_count[n] = k + 1;  // (m > 0: at least one is kept)
+    const int i = (int)((key >> 8) & 0xffffffu);
+    int64_t row;
+    int a;
+    cand_locate(p, A, n, i, row, a);
+    decode_one<T>(anchors + (size_t)i * 4, box + row * ldb + a * 4, out_boxes + ((size_t)n * max_out + k) * 4);
+    out_cls[(size_t)n * max_out + k] = (int)(key & 0xffu);
+    const float v = desc_float((uint32_t)(key >> 32));
+    out_scores[(size_t)n * max_out + k] = SOFT ? v : 1.0f / (1.0f + expf(-v));
+  }
+}
+
 // One 1024-thread block per image.  Dynamic LDS: keys[pcap] (8 B) then boxes[cap] (16 B), pcap
 // the power of two at or above cap.
 template <typename T>
@@ -537,28 +600,8 @@ __global__ __launch_bounds__(1024) void k_nms_pc(const float* anchors, edet_pyra
     if (tid == 0) out_count[n] = 0;
     return;
   }
-  int P = 1;
-  while (P < m) P <<= 1;
-  for (int q = tid; q < P; q += blockDim.x) keys[q] = (q < m) ? cand[(size_t)n * cap + q] : KEY_SENTINEL;
-  if (tid < 256) { cstart[tid] = 0; cend[tid] = 0; }
   if (tid == 0) next_cls = 1;
-  __syncthreads();
-  bitonic_sort(keys, P);  // class ascending, logit descending, anchor ascending
-
-  // boxes of the sorted candidates, and the class segments [cstart, cend)
-  for (int q = tid; q < m; q += blockDim.x) {
-    const uint64_t k = keys[q];
-    const int i = (int)(k & 0xffffffu), c = (int)(k >> 56);
-    int64_t row;
-    int a;
-    cand_locate(p, A, n, i, row, a);
-    float bx[4];
-    decode_one<T>(anchors + (size_t)i * 4, box + row * ldb + a * 4, bx);
-    boxes[q] = make_float4(bx[0], bx[1], bx[2], bx[3]);
-    if (q == 0 || (int)(keys[q - 1] >> 56) != c) cstart[c] = q;
-    if (q == m - 1 || (int)(keys[q + 1] >> 56) != c) cend[c] = q + 1;
-  }
-  __syncthreads();
+  const int P = sort_candidates<T>(anchors, p, A, box, ldb, cand + (size_t)n * cap, n, m, keys, boxes, cstart, cend);
 
   // Greedy NMS, a wave per class.  The class's kept boxes are compacted to the front of its
   // own segment of `boxes` (kept box k at s0 + k, never past the candidate being resolved, and
@@ -606,32 +649,224 @@ __global__ __launch_bounds__(1024) void k_nms_pc(const float* anchors, edet_pyra
   __syncthreads();
   bitonic_sort(keys, P);  // logit descending, anchor ascending, class ascending; dropped last
 
-  const int lim = min(max_out, m);
-  for (int k = tid; k < lim; k += blockDim.x) {
-    const uint64_t key = keys[k];
-    if (key == KEY_SENTINEL) continue;
-    if (k + 1 == lim || keys[k + 1] == KEY_SENTINEL) out_count[n] = k + 1;  // (m > 0: at least one is kept)
-    const int i = (int)((key >> 8) & 0xffffffu);
-    int64_t row;
-    int a;
-    cand_locate(p, A, n, i, row, a);
-    // the kept box again from its regression: the compaction above reused the LDS boxes
-    decode_one<T>(anchors + (size_t)i * 4, box + row * ldb + a * 4, out_boxes + ((size_t)n * max_out + k) * 4);
-    out_cls[(size_t)n * max_out + k] = (int)(key & 0xffu);
-    out_scores[(size_t)n * max_out + k] = 1.0f / (1.0f + expf(-desc_float((uint32_t)(key >> 32))));
+  write_detections<T, false>(anchors, p, A, box, ldb, keys, n, m, max_out, out_boxes, out_cls, out_scores, out_count);
+}
+
+// ---------------------------------------------------------------- Gaussian Soft-NMS
+// Per class: pick the live candidate with the largest score s (fp64; on equal s the lower
+// anchor), emit it, multiply every other live s_j by exp(-iou^2 / sigma), drop j once s_j <
+// min_score; until the class is empty or has max_out picks.  The winner of a round depends on
+// every earlier decay, so the class's live list is swept once per pick.  A sweep ("pass") does
+// three things to each live candidate: the decay by the current pick, the min_score test, and
+// its share of the arg-max under (s descending, anchor ascending), which is the next pick.
+// The live list sits at the front of the class's own segment of keys / boxes / score and is
+// compacted in place by every pass (ballot + popcount prefix, candidates keep their order), so
+// passes shrink as candidates retire or drop.  Emission k of a class goes to the segment's slot
+// s1 - 1 - k: live + emitted + dropped is the segment's size, so that slot is behind the live
+// list once the pass that retired the pick has run.
+//
+// Work split: a class whose segment has at most SOFT_WAVE_MAX candidates is swept by one wave
+// (classes claimed from a counter, as in k_nms_pc); a larger one by the whole block afterwards,
+// 1024 candidates per round.  A block pass pays one barrier per round, one for the cross-wave
+// arg-max and the 16-entry LDS reduction, about the time of three to four 64-candidate tiles of
+// a wave pass; a wave working alone breaks even there, hence 256 = four tiles.  (A segment is
+// never re-routed: a block class whose live list shrinks under 256 stays with the block.)
+//
+// Arithmetic: overlap (iou_tf64, the op order of iou_tf), decay and scores are fp64 without
+// contraction; IEEE add / mul / div are the same bits on any conforming machine, so against an
+// fp64 host restatement in the same order only exp differs: <= 1 ulp here (the HIP math API's
+// documented bound for the double exp) plus <= 1 ulp there, and the product's own rounding moves
+// by <= 1 ulp with it.  That is <= 3 ulp = 6.7e-16 relative per decay, <= 7e-14 after 100
+// decays (the initial sigmoid adds 2 ulp once).  The score is rounded to fp32 once, on emission.
+constexpr int SOFT_WAVE_MAX = 256;
+
+// arg-max operand: the score's bits (s >= 0, so their unsigned order is the order of s) and
+// (2^24 - 1 - anchor) << 12 | position (24 + 12 bits), so the larger tag is the lower anchor.
+// A real tag is never 0 (anchor < 2^24 - 1), so {0, 0} loses to every candidate.
+struct SoftBest {
+  uint64_t sb, tag;
+};
+__device__ __forceinline__ SoftBest soft_better(SoftBest a, SoftBest b) {
+  return (b.sb > a.sb || (b.sb == a.sb && b.tag > a.tag)) ? b : a;
+}
+__device__ __forceinline__ SoftBest soft_xor(SoftBest v, int o) {
+  SoftBest r;
+  r.sb = (uint64_t)__shfl_xor((unsigned long long)v.sb, o, 64);
+  r.tag = (uint64_t)__shfl_xor((unsigned long long)v.tag, o, 64);
+  return r;
+}
+
+// One pass over the live list [s0, s0 + L) of a class, by one wave (BLOCK = false) or by the
+// whole block (every thread calls it, with block-uniform arguments).  DECAY: the candidate at
+// ppos is retired and the others decay by the pick's box pb; without it (the first pass) nothing
+// moves.  Returns the new live count; best is the arg-max over the new list, its position the
+// compacted one.  Both are uniform over the wave / block.  wsum: [2][16] ints, wbest: [16]
+// entries, block mode only; the caller alternates wbest between passes.
+template <bool BLOCK, bool DECAY>
+__device__ __forceinline__ int soft_pass(uint64_t* keys, float4* boxes, double* score, int s0, int L, int ppos,
+                                         const double* pb, double sigma, double min_score, int* wsum,
+                                         SoftBest* wbest, SoftBest& best) {
+  constexpr int STEP = BLOCK ? 1024 : 64;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, me = BLOCK ? (int)threadIdx.x : lane;
+  const uint64_t lt = (1ull << lane) - 1ull;
+  SoftBest mine = {0ull, 0u};
+  int run = 0;  // live candidates written so far, the same in every thread
+  for (int t0 = 0, r = 0; t0 < L; t0 += STEP, r ^= 1) {
+    const bool valid = t0 + me < L;
+    const int q = s0 + (valid ? t0 + me : 0);
+    const uint64_t key = keys[q];
+    const float4 bq = boxes[q];
+    double s = score[q];
+    if constexpr (!BLOCK) {  // the tile is in registers before any lane writes into it
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
+    bool keep = valid;
+    if constexpr (DECAY) {
+      keep = valid && q != ppos;
+      if (keep) {
+        const double b[4] = {bq.x, bq.y, bq.z, bq.w};
+        const double ov = iou_tf64(pb, b);
+        s = s * exp(-(ov * ov) / sigma);
+        keep = !(s < min_score);
+      }
+    }
+    const uint64_t bal = __ballot(keep);
+    int np = s0 + run + __popcll(bal & lt);
+    if constexpr (BLOCK) {
+      if (lane == 0) wsum[r * 16 + wave] = __popcll(bal);
+      __syncthreads();  // (one per round: the two wsum rows alternate; every read of the round is done)
+#pragma unroll
+      for (int w = 0; w < 16; ++w) {
+        const int t = wsum[r * 16 + w];
+        np += (w < wave) ? t : 0;
+        run += t;
+      }
+    } else {
+      run += __popcll(bal);
+    }
+    if (keep) {  // np <= q: never ahead of what this round or tile has read
+      if constexpr (DECAY) {
+        keys[np] = key;
+        boxes[np] = bq;
+        score[np] = s;
+      }
+      const SoftBest c = {(uint64_t)__double_as_longlong(s),
+                          ((0xffffffull - (key & 0xffffffull)) << 12) | (uint64_t)np};
+      mine = soft_better(mine, c);
+    }
+    if constexpr (!BLOCK) {  // the next tile, and the caller, read this tile's writes
+      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+    }
   }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine = soft_better(mine, soft_xor(mine, o));
+  if constexpr (BLOCK) {
+    if (lane == 0) wbest[wave] = mine;
+    __syncthreads();
+    mine = wbest[lane & 15];
+#pragma unroll
+    for (int o = 8; o > 0; o >>= 1) mine = soft_better(mine, soft_xor(mine, o));
+  }
+  best = mine;
+  return run;
+}
+
+// Soft-NMS of class c, segment [s0, s1), by one wave or by the whole block.  On return the
+// segment's keys are the class's output keys (fp32 score descending | anchor | class) at its
+// end and the sentinel before them.
+template <bool BLOCK>
+__device__ __forceinline__ void soft_class(uint64_t* keys, float4* boxes, double* score, int c, int s0, int s1,
+                                           int max_out, double sigma, double min_score, int* wsum,
+                                           SoftBest* wbest) {
+  const int me = BLOCK ? (int)threadIdx.x : (int)(threadIdx.x & 63), step = BLOCK ? 1024 : 64;
+  const double none[4] = {0.0, 0.0, 0.0, 0.0};
+  SoftBest best;
+  int L = soft_pass<BLOCK, false>(keys, boxes, score, s0, s1 - s0, -1, none, sigma, min_score, wsum, wbest, best);
+  int k = 0;
+  while (L > 0 && k < max_out) {
+    const int pos = (int)(best.tag & 0xfffu);
+    const uint64_t anchor = 0xffffffull - (best.tag >> 12);
+    const float sc = (float)__longlong_as_double((long long)best.sb);  // the one rounding to fp32
+    const uint64_t okey = ((uint64_t)desc_bits(sc) << 32) | (anchor << 8) | (uint64_t)c;
+    if (k + 1 < max_out) {  // (the class's last pick decays nobody)
+      const float4 pq = boxes[pos];
+      const double pb[4] = {pq.x, pq.y, pq.z, pq.w};
+      L = soft_pass<BLOCK, true>(keys, boxes, score, s0, L, pos, pb, sigma, min_score, wsum,
+                                 wbest + ((k & 1) ? 0 : 16), best);
+    } else {
+      L = 0;
+    }
+    if (me == 0) keys[s1 - 1 - k] = okey;  // behind the live list (header)
+    ++k;
+  }
+  for (int q = s0 + me; q < s1 - k; q += step) keys[q] = KEY_SENTINEL;
+}
+
+// One 1024-thread block per image.  Dynamic LDS: keys[pcap] (8 B), boxes[cap] (16 B), score[cap]
+// (8 B): 128 KiB at cap = 4096.
+template <typename T>
+__global__ __launch_bounds__(1024) void k_softnms_pc(const float* anchors, edet_pyramid p, int A, const T* box,
+                                                     int ldb, int NC, const uint64_t* cand, const int32_t* total,
+                                                     int cap, int pcap, int max_out, double sigma, double min_score,
+                                                     float* out_boxes, int32_t* out_cls, float* out_scores,
+                                                     int32_t* out_count) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  __shared__ int cstart[256], cend[256];
+  __shared__ int next_cls;
+  __shared__ int wsum[2 * 16];
+  __shared__ SoftBest wbest[2 * 16];
+  uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
+  float4* boxes = reinterpret_cast<float4*>(smem + (size_t)pcap * 8);
+  double* score = reinterpret_cast<double*>(smem + (size_t)pcap * 8 + (size_t)cap * 16);
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const int m = min(total[n], cap);
+  if (m == 0) {  // block-uniform
+    if (tid == 0) out_count[n] = 0;
+    return;
+  }
+  if (tid == 0) next_cls = 1;
+  const int P = sort_candidates<T>(anchors, p, A, box, ldb, cand + (size_t)n * cap, n, m, keys, boxes, cstart, cend);
+  for (int q = tid; q < m; q += blockDim.x)
+    score[q] = 1.0 / (1.0 + exp(-(double)desc_float((uint32_t)(keys[q] >> 24))));
+  __syncthreads();
+
+  for (;;) {  // small classes, a wave each
+    int c = 0;
+    if (lane == 0) c = atomicAdd(&next_cls, 1);  // which wave takes a class does not reach the result
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= NC) break;
+    const int s0 = cstart[c], s1 = cend[c];
+    if (s1 > s0 && s1 - s0 <= SOFT_WAVE_MAX)
+      soft_class<false>(keys, boxes, score, c, s0, s1, max_out, sigma, min_score, wsum, wbest);
+  }
+  __syncthreads();
+  for (int c = 1; c < NC; ++c) {  // large classes, the whole block each
+    const int s0 = cstart[c], s1 = cend[c];
+    if (s1 - s0 > SOFT_WAVE_MAX) soft_class<true>(keys, boxes, score, c, s0, s1, max_out, sigma, min_score, wsum, wbest);
+  }
+  __syncthreads();
+  bitonic_sort(keys, P);  // score descending, anchor ascending, class ascending; the rest last
+
+  write_detections<T, true>(anchors, p, A, box, ldb, keys, n, m, max_out, out_boxes, out_cls, out_scores, out_count);
 }
 
 }  // namespace edet
 
 using namespace edet;
 
-// both entry points; select is validated by the caller
+// Gaussian Soft-NMS in place of the hard kernel (validated by edet_detect_per_class_soft)
+struct SoftNms {
+  double sigma, min_score;
+};
+
+// every entry point; select and soft are validated by the caller.  soft == nullptr: hard NMS.
 static int detect_per_class_run(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
                                 const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float iou_thr,
-                                float logit_thr, int metric, int select, void* scratch, float* out_boxes,
-                                int32_t* out_cls, float* out_scores, int32_t* out_count, int32_t* out_total,
-                                int32_t* out_overflow, edet_stream_t stream) {
+                                float logit_thr, int metric, int select, const SoftNms* soft, void* scratch,
+                                float* out_boxes, int32_t* out_cls, float* out_scores, int32_t* out_count,
+                                int32_t* out_total, int32_t* out_overflow, edet_stream_t stream) {
   EDET_REQUIRE(anchors && box && cls && p && scratch && out_boxes && out_cls && out_scores && out_count &&
                    out_total && out_overflow,
                "detect_per_class: null argument");
@@ -669,13 +904,17 @@ static int detect_per_class_run(int dtype, const float* anchors, const void* box
   const int cap = max_candidates;
   int pcap = 2;  // (at least 16 bytes of keys: the boxes behind them stay 16-byte aligned)
   while (pcap < max_candidates) pcap <<= 1;
-  const size_t lds = (size_t)pcap * 8 + (size_t)max_candidates * 16;
+  // keys and boxes; Soft-NMS adds an fp64 score per candidate
+  const size_t lds = (size_t)pcap * 8 + (size_t)max_candidates * (soft ? 24 : 16);
+  EDET_REQUIRE(lds <= 156 * 1024, "detect_per_class: %zu bytes of LDS for %d candidates, a block has 160 KiB",
+               lds, max_candidates);  // (the kernels' static LDS is under 4 KiB)
   const hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)(p->batch * nbi));
   EDET_DTYPE_DISPATCH(dtype, T, {
     if (lds > 48 * 1024) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_nms_pc<T>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      const void* fn = soft ? reinterpret_cast<const void*>(&k_softnms_pc<T>)
+                            : reinterpret_cast<const void*>(&k_nms_pc<T>);
+      const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) {
         set_error("detect_per_class: %zu bytes of LDS: %s", lds, hipGetErrorString(e));
         return EDET_EHIP;
@@ -699,9 +938,14 @@ static int detect_per_class_run(int dtype, const float* anchors, const void* box
       EDET_LAUNCH(k_sel_write<T>, grid, dim3(DET_THREADS), 0, st, lg, ldc, *p, A, NC, nbi, logit_thr, cap, out_total,
                   state, cgt, ceq, cand);
     }
-    EDET_LAUNCH(k_nms_pc<T>, dim3(p->batch), dim3(1024), lds, st, anchors, *p, A, (const T*)box, ldb, NC, cand,
-                out_total, max_candidates, pcap, max_out, iou_thr, metric == EDET_OVERLAP_DIOU ? 1 : 0, out_boxes,
-                out_cls, out_scores, out_count);
+    if (soft)
+      EDET_LAUNCH(k_softnms_pc<T>, dim3(p->batch), dim3(1024), lds, st, anchors, *p, A, (const T*)box, ldb, NC, cand,
+                  out_total, max_candidates, pcap, max_out, soft->sigma, soft->min_score, out_boxes, out_cls,
+                  out_scores, out_count);
+    else
+      EDET_LAUNCH(k_nms_pc<T>, dim3(p->batch), dim3(1024), lds, st, anchors, *p, A, (const T*)box, ldb, NC, cand,
+                  out_total, max_candidates, pcap, max_out, iou_thr, metric == EDET_OVERLAP_DIOU ? 1 : 0, out_boxes,
+                  out_cls, out_scores, out_count);
     return check_launch("edet detect_per_class");
   });
 }
@@ -714,7 +958,7 @@ int edet_detect_per_class(int dtype, const float* anchors, const void* box, int 
                           float* out_scores, int32_t* out_count, int32_t* out_total, int32_t* out_overflow,
                           edet_stream_t stream) {
   return detect_per_class_run(dtype, anchors, box, ldb, cls, ldc, p, A, NC, max_candidates, max_out, iou_thr,
-                              logit_thr, metric, EDET_SELECT_FIRST, scratch, out_boxes, out_cls, out_scores, out_count,
+                              logit_thr, metric, EDET_SELECT_FIRST, nullptr, scratch, out_boxes, out_cls, out_scores, out_count,
                               out_total, out_overflow, stream);
 }
 
@@ -726,7 +970,23 @@ int edet_detect_per_class_select(int dtype, const float* anchors, const void* bo
   EDET_REQUIRE(select == EDET_SELECT_FIRST || select == EDET_SELECT_TOPK,
                "detect_per_class: select %d is neither EDET_SELECT_FIRST nor EDET_SELECT_TOPK", select);
   return detect_per_class_run(dtype, anchors, box, ldb, cls, ldc, p, A, NC, max_candidates, max_out, iou_thr,
-                              logit_thr, metric, select, scratch, out_boxes, out_cls, out_scores, out_count, out_total,
+                              logit_thr, metric, select, nullptr, scratch, out_boxes, out_cls, out_scores, out_count,
+                              out_total, out_overflow, stream);
+}
+
+int edet_detect_per_class_soft(int dtype, const float* anchors, const void* box, int ldb, const void* cls, int ldc,
+                               const edet_pyramid* p, int A, int NC, int max_candidates, int max_out, float logit_thr,
+                               int metric, int select, double sigma, double min_score, void* scratch,
+                               float* out_boxes, int32_t* out_cls, float* out_scores, int32_t* out_count,
+                               int32_t* out_total, int32_t* out_overflow, edet_stream_t stream) {
+  EDET_REQUIRE(select == EDET_SELECT_FIRST || select == EDET_SELECT_TOPK,
+               "detect_per_class_soft: select %d is neither EDET_SELECT_FIRST nor EDET_SELECT_TOPK", select);
+  EDET_REQUIRE(metric == EDET_OVERLAP_IOU, "detect_per_class_soft: metric %d, Soft-NMS decays by the IoU only", metric);
+  EDET_REQUIRE(sigma > 0.0 && sigma <= DBL_MAX, "detect_per_class_soft: sigma %g is not positive and finite", sigma);
+  EDET_REQUIRE(min_score >= 0.0 && min_score < 1.0, "detect_per_class_soft: min_score %g outside [0, 1)", min_score);
+  const SoftNms soft = {sigma, min_score};
+  return detect_per_class_run(dtype, anchors, box, ldb, cls, ldc, p, A, NC, max_candidates, max_out, 0.f, logit_thr,
+                              metric, select, &soft, scratch, out_boxes, out_cls, out_scores, out_count, out_total,
                               out_overflow, stream);
 }
 

@@ -457,8 +457,9 @@ class EfficientDetNetTrain(EfficientDetNet):
         self.grad_allreduce = grad_allreduce
         self.npos_allreduce = npos_allreduce
         # test_step's detections: "reference" (convert_outputs_one: one class per anchor, class-
-        # agnostic DIoU-NMS), "per_class" (Anchors.detect_per_class: multi-label, NMS per class) or
+        # agnostic DIoU-NMS), "per_class" (Anchors.detect_per_class: multi-label, NMS per class),
         # "per_class_topk" (the same with select="topk": the best candidates by score on overflow)
+        # or "per_class_soft" (select="topk" with nms="soft": Gaussian Soft-NMS per class)
         self.detect_mode = "reference"
         # each data-parallel replica draws its own drop-connect masks (MirroredStrategy replicas
         # draw tf.random.uniform independently, drop_connect.py:13): fold the rank into the seed
@@ -623,14 +624,15 @@ class EfficientDetNetTrain(EfficientDetNet):
         P = self.P  # _reg_l2_loss (efficientdet_net_train.py:21-28): the L2 prefix of the flat weights
         l2 = 4e-5 * 0.5 * float((P.w[: P.n_l2].double() ** 2).sum())
         loss = float(sc[0]) + l2
-        if self.detect_mode in ("per_class", "per_class_topk"):
-            sel = "topk" if self.detect_mode == "per_class_topk" else "first"
-            ob, oc, os_, cnt = self.anchors.detect_per_class(boxes_out, classes_out, select=sel)[:4]
+        if self.detect_mode in ("per_class", "per_class_topk", "per_class_soft"):
+            sel = "first" if self.detect_mode == "per_class" else "topk"
+            nms = "soft" if self.detect_mode == "per_class_soft" else "hard"
+            ob, oc, os_, cnt = self.anchors.detect_per_class(boxes_out, classes_out, select=sel, nms=nms)[:4]
         elif self.detect_mode == "reference":
             ob, oc, os_, cnt = self.anchors.detect(self.anchors.convert_outputs_boxes(boxes_out), classes_out)
         else:
-            raise ValueError(f"detect_mode {self.detect_mode!r}: expected 'reference', 'per_class' or "
-                             f"'per_class_topk'")
+            raise ValueError(f"detect_mode {self.detect_mode!r}: expected 'reference', 'per_class', "
+                             f"'per_class_topk' or 'per_class_soft'")
         ob, oc, os_, cnt = ob.cpu().numpy(), oc.cpu().numpy(), os_.cpu().numpy(), cnt.cpu().numpy()
         rb = np.asarray(real_boxes.cpu() if isinstance(real_boxes, torch.Tensor) else real_boxes, np.float64)
         rc = np.asarray(real_classes.cpu() if isinstance(real_classes, torch.Tensor) else real_classes, np.float64)
