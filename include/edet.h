@@ -406,6 +406,42 @@ int edet_detection_loss(int dtype, const void* cls, int ldc, const void* box, in
                         const float* box_t, const float* npos_sum, float alpha, float gamma,
                         float delta, float box_weight, float focal_count_scale, void* dcls,
                         void* dbox, float* loss, float* level_parts, edet_stream_t stream);
+/* The same loss with an IoU-family term on the decoded boxes of the positive anchors (the
+ * iou_loss_type / iou_loss_weight option of the published EfficientDet recipe).  Arguments as
+ * edet_detection_loss, plus anchors fp32 [N][4] (y1, x1, y2, x2; N = sum_l H_l*W_l*A, indexed as
+ * by edet_decode_boxes), mask [rows][A] (non-zero: positive anchor; rows outside the levels are
+ * not read), iou_kind, iou_weight (finite, >= 0) and iou_parts (nullable, EDET_MAX_SEG floats).
+ *
+ * For every anchor with mask != 0, with (ha, wa, yca, xca) the anchor's sides and centre and
+ * CLIP = log(1000/16), both the predicted and the target regressions (ty, tx, th, tw) decode as
+ *   h = exp(clamp(th, -CLIP, CLIP)) ha,  w = exp(clamp(tw, -CLIP, CLIP)) wa,
+ *   yc = ty ha + yca,  xc = tx wa + xca,  box = (yc - h/2, xc - w/2, yc + h/2, xc + w/2)
+ * giving P and T (the clamp is for this term only; a clamped predicted component gets no IoU
+ * gradient).  inter = max(0, min(P.y2, T.y2) - max(P.y1, T.y1)) * (the same in x),
+ * U = area(P) + area(T) - inter, iou = inter / U; ey, ex the sides of the enclosing box,
+ * C = ey ex, c2 = ey^2 + ex^2, rho2 = (P.yc - T.yc)^2 + (P.xc - T.xc)^2.  L = 1 - iou + pen:
+ *   EDET_IOU_LOSS_IOU   pen = 0
+ *   EDET_IOU_LOSS_GIOU  pen = (C - U) / C
+ *   EDET_IOU_LOSS_DIOU  pen = rho2 / c2
+ *   EDET_IOU_LOSS_CIOU  pen = rho2 / c2 + alpha v,  v = (4/pi^2) (atan(T.w/T.h) - atan(P.w/P.h))^2,
+ *                       alpha = v / ((1 - iou) + v), a constant in the backward
+ * A ratio whose denominator is exactly 0 is 0 and has no gradient.  Per level, with N+ =
+ * npos_sum + 1:  iou_l = sum_pos L / N+,  loss += iou_weight * iou_l,  iou_parts[l] += iou_l.
+ * dbox receives d loss / d box of the Huber and the IoU term together (added in fp32, rounded to
+ * dtype once); anchors with mask == 0 get the Huber gradient alone, bit for bit what
+ * edet_detection_loss writes.  dbox may alias box, be a separate buffer or be null.
+ * Two launches: the class blocks of the plain loss, then one kernel for the box branch. */
+#define EDET_IOU_LOSS_IOU 0
+#define EDET_IOU_LOSS_GIOU 1
+#define EDET_IOU_LOSS_DIOU 2
+#define EDET_IOU_LOSS_CIOU 3
+int edet_detection_loss_iou(int dtype, const void* cls, int ldc, const void* box, int ldb,
+                            const edet_pyramid* p, int A, int NC, const int32_t* cls_t,
+                            const float* box_t, const float* npos_sum, float alpha, float gamma,
+                            float delta, float box_weight, float focal_count_scale, void* dcls,
+                            void* dbox, float* loss, float* level_parts, const float* anchors,
+                            const uint8_t* mask, int iou_kind, float iou_weight, float* iou_parts,
+                            edet_stream_t stream);
 int edet_count_positives(const uint8_t* mask, int64_t n, float* out, edet_stream_t stream);
 int edet_onehot_to_index(const float* onehot, int64_t n, int NC, int32_t* out,
                          edet_stream_t stream);

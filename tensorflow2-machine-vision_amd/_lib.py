@@ -54,6 +54,7 @@ def stat_unfold(v):
 DETECT_MAX_CANDIDATES, DETECT_CHUNK_ROWS = 4096, 16  # EDET_DETECT_MAX_CANDIDATES, EDET_DETECT_CHUNK_ROWS
 OVERLAP = {"iou": 0, "diou": 1}  # EDET_OVERLAP_IOU, EDET_OVERLAP_DIOU
 SELECT = {"first": 0, "topk": 1}  # EDET_SELECT_FIRST, EDET_SELECT_TOPK
+IOU_LOSS = {"iou": 0, "giou": 1, "diou": 2, "ciou": 3}  # EDET_IOU_LOSS_IOU / GIOU / DIOU / CIOU
 
 
 def detect_scratch_bytes(batch: int, max_candidates: int, nbi: int, select: int = 0) -> int:
@@ -188,6 +189,8 @@ SIGNATURES = {
     "edet_bifpn_fuse_fold": [c_int, POINTER(FuseFold), P],
     "edet_detection_loss": [c_int, P, c_int, P, c_int, PPyr, c_int, c_int, P, P, P, c_float,
                             c_float, c_float, c_float, c_float, P, P, P, P, P],
+    "edet_detection_loss_iou": [c_int, P, c_int, P, c_int, PPyr, c_int, c_int, P, P, P, c_float,
+                                c_float, c_float, c_float, c_float, P, P, P, P, P, P, c_int, c_float, P, P],
     "edet_count_positives": [P, c_int64, P, P],
     "edet_onehot_to_index": [P, c_int64, c_int, P, P],
     "edet_anchor_boxes": [c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P, P],

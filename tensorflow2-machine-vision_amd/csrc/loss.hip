@@ -8,6 +8,7 @@
 //   box_l   = sum huber(pred - t) * [t != 0] / (4 N+)
 //   loss   += box_weight * box_l + focal_l
 // The one-hot class target of the reference (anchors.py:133) is represented by its index.
+#include <float.h>
 #include "common.hpp"
 
 namespace edet {
@@ -276,6 +277,294 @@ __global__ __launch_bounds__(256) void k_loss(LossArgs g) {
   }
 }
 
+// ------------------------------------------------------------------ box branch with an IoU term
+// edet_detection_loss_iou: Huber as in k_loss's box blocks plus an IoU-family loss on the
+// decoded boxes of the positive anchors (include/edet.h has the definition).  The predictions
+// are overwritten by their gradient, so both terms come from the same loaded values and their
+// summed gradient is stored once.
+//
+// Work split.  A block owns one LBOX_ROWS chunk of a level, a thread owns whole anchors: the four
+// regressions as one 8-byte (bf16) or 16-byte (f32) vector, the four targets as one float4, the
+// mask byte.  Positives are well under 1 % of the anchors in training, so the IoU arithmetic
+// (about 150 VALU instructions, an exp pair, divisions) would run at one or two live lanes per
+// wave if each owner did its own.  Instead:
+//   phase 1  every thread walks its anchors: Huber value and gradient in registers; a
+//            non-positive anchor's gradient is stored at once.  Each wave ballots its positives
+//            and appends them (slot, predictions, targets) to its own IOU_WCAP-entry region of an
+//            LDS list -- a wave-private counter, no atomics, no barrier, a fixed order.
+//   barrier  one __syncthreads per block.
+//   phase 2  the four regions are walked as one dense list, one lane per positive: the lane
+//            recomputes the entry's Huber gradient (the same function, the same bits), adds the
+//            IoU gradient in fp32 and does the anchor's single vector store.
+// A positive that finds its wave's region full (dense synthetic masks; training never gets
+// near) is handled by its owner in phase 1 with the same arithmetic.
+constexpr int IOU_WCAP = 64;
+constexpr float BOX_CLIP = 4.135166556742356f;  // log(1000 / 16)
+
+struct BoxIouArgs {
+  const void* box;
+  const float* box_t;
+  const float* npos;
+  const float* anchors;
+  const uint8_t* mask;
+  void* dbox;
+  float* loss;
+  float* parts;
+  float* iou_parts;
+  edet_pyramid p;
+  int ldb, A;
+  float delta, box_weight, iou_weight;
+  int vec;
+};
+
+// four contiguous elements -> fp32; vec: the pointer is aligned for one vector access
+__device__ __forceinline__ void ld4(const float* p, bool vec, float* o) {
+  if (vec) {
+    const float4 v = *reinterpret_cast<const float4*>(p);
+    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = p[j];
+  }
+}
+__device__ __forceinline__ void ld4(const uint16_t* p, bool vec, float* o) {
+  if (vec) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
+    o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = bf2f(p[j]);
+  }
+}
+__device__ __forceinline__ void st4(float* p, bool vec, const float* v) {
+  if (vec) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = v[j];
+  }
+}
+__device__ __forceinline__ void st4(uint16_t* p, bool vec, const float* v) {
+  if (vec) {
+    *reinterpret_cast<uint2*>(p) = make_uint2((uint32_t)f2bf(v[0]) | ((uint32_t)f2bf(v[1]) << 16),
+                                              (uint32_t)f2bf(v[2]) | ((uint32_t)f2bf(v[3]) << 16));
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p[j] = f2bf(v[j]);
+  }
+}
+
+// Huber of one anchor's four components in k_loss's arithmetic (the same expressions, so an
+// anchor without an IoU term gets the bits edet_detection_loss writes): returns sum h * [t != 0],
+// d[j] = d(box_weight * box_l) / d pred[j]
+__device__ __forceinline__ float huber4(const float* p, const float* t, float dl, float inv, float bw, float* d) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const float mask = (t[j] != 0.f) ? 1.f : 0.f;
+    const float err = p[j] - t[j], ae = fabsf(err);
+    const float h = (ae <= dl) ? 0.5f * err * err : 0.5f * dl * dl + dl * (ae - dl);
+    s += h * mask;
+    const float dh = (ae <= dl) ? err : (err > 0.f ? dl : -dl);
+    d[j] = dh * mask * inv * bw;
+  }
+  return s;
+}
+
+// 1 / d, and 0 for d == 0: a ratio with a zero denominator is 0 and has no gradient
+__device__ __forceinline__ float rcp0(float d) { return d == 0.f ? 0.f : 1.f / d; }
+
+// centre / size form of an anchor's regressions (ty, tx, th, tw), th and tw clamped to +-BOX_CLIP
+struct CSBox { float yc, xc, h, w; };
+__device__ __forceinline__ CSBox decode_clamped(const float* r, float ha, float wa, float yca, float xca) {
+  CSBox b;
+  b.h = expf(fminf(fmaxf(r[2], -BOX_CLIP), BOX_CLIP)) * ha;
+  b.w = expf(fminf(fmaxf(r[3], -BOX_CLIP), BOX_CLIP)) * wa;
+  b.yc = r[0] * ha + yca;
+  b.xc = r[1] * wa + xca;
+  return b;
+}
+
+// One positive anchor: L = 1 - iou + penalty(KIND) of the decoded prediction p against the decoded
+// target t, and gi[j] = dL / d p[j].  Backward by hand: the gradient is collected on the
+// intersection area (gI), the predicted area (gA), the enclosing sides (gey, gex) and the
+// predicted centre and size, then taken through the corners and the decode.  min / max pass
+// their gradient to the predicted box where it is strictly the selected argument.
+template <int KIND>
+__device__ __forceinline__ float iou_term(const float* p, const float* t, const float* an, float* gi) {
+  const float ha = an[2] - an[0], wa = an[3] - an[1];
+  const float yca = 0.5f * (an[0] + an[2]), xca = 0.5f * (an[1] + an[3]);
+  const CSBox P = decode_clamped(p, ha, wa, yca, xca), T = decode_clamped(t, ha, wa, yca, xca);
+  const float py1 = P.yc - 0.5f * P.h, py2 = P.yc + 0.5f * P.h, px1 = P.xc - 0.5f * P.w, px2 = P.xc + 0.5f * P.w;
+  const float ty1 = T.yc - 0.5f * T.h, ty2 = T.yc + 0.5f * T.h, tx1 = T.xc - 0.5f * T.w, tx2 = T.xc + 0.5f * T.w;
+  const float dyi = fminf(py2, ty2) - fmaxf(py1, ty1), dxi = fminf(px2, tx2) - fmaxf(px1, tx1);
+  const float ih = fmaxf(dyi, 0.f), iw = fmaxf(dxi, 0.f);
+  const float inter = ih * iw;
+  const float U = P.h * P.w + T.h * T.w - inter;
+  const float rU = rcp0(U);
+  const float iou = inter * rU;
+  float L = 1.f - iou;
+  float gI = -(U + inter) * rU * rU, gA = inter * rU * rU;  // d(-iou) / d inter, / d area(P)
+  float gyc = 0.f, gxc = 0.f, gh = 0.f, gw = 0.f, gey = 0.f, gex = 0.f;
+  if (KIND != EDET_IOU_LOSS_IOU) {
+    const float ey = fmaxf(py2, ty2) - fminf(py1, ty1), ex = fmaxf(px2, tx2) - fminf(px1, tx1);
+    if (KIND == EDET_IOU_LOSS_GIOU) {
+      const float C = ey * ex, rC = rcp0(C);
+      L += (C - U) * rC;  // 1 - U / C
+      gI += rC;
+      gA -= rC;
+      gey = U * rC * rC * ex;
+      gex = U * rC * rC * ey;
+    } else {
+      const float r2 = rcp0(ey * ey + ex * ex);
+      const float dy = P.yc - T.yc, dx = P.xc - T.xc, rho2 = dy * dy + dx * dx;
+      L += rho2 * r2;
+      gyc = 2.f * dy * r2;
+      gxc = 2.f * dx * r2;
+      gey = -2.f * rho2 * r2 * r2 * ey;
+      gex = -2.f * rho2 * r2 * r2 * ex;
+      if (KIND == EDET_IOU_LOSS_CIOU) {
+        const float k = 0.40528473456935109f;  // 4 / pi^2
+        const float da = atanf(T.w * rcp0(T.h)) - atanf(P.w * rcp0(P.h));
+        const float v = k * da * da;
+        const float al = v * rcp0((1.f - iou) + v);  // a constant in the backward
+        L += al * v;
+        // d atan(w / h) = (h dw - w dh) / (h^2 + w^2)
+        const float sv = P.h == 0.f ? 0.f : -2.f * k * da * al * rcp0(P.h * P.h + P.w * P.w);
+        gw += sv * P.h;
+        gh -= sv * P.w;
+      }
+    }
+  }
+  const float gih = dyi > 0.f ? gI * iw : 0.f, giw = dxi > 0.f ? gI * ih : 0.f;
+  const float gy1 = (py1 > ty1 ? -gih : 0.f) - (py1 < ty1 ? gey : 0.f);
+  const float gy2 = (py2 < ty2 ? gih : 0.f) + (py2 > ty2 ? gey : 0.f);
+  const float gx1 = (px1 > tx1 ? -giw : 0.f) - (px1 < tx1 ? gex : 0.f);
+  const float gx2 = (px2 < tx2 ? giw : 0.f) + (px2 > tx2 ? gex : 0.f);
+  gyc += gy1 + gy2;
+  gxc += gx1 + gx2;
+  gh += 0.5f * (gy2 - gy1) + gA * P.w;
+  gw += 0.5f * (gx2 - gx1) + gA * P.h;
+  gi[0] = gyc * ha;
+  gi[1] = gxc * wa;
+  gi[2] = fabsf(p[2]) <= BOX_CLIP ? gh * P.h : 0.f;  // d exp(th) ha / d th; nothing through the clamp
+  gi[3] = fabsf(p[3]) <= BOX_CLIP ? gw * P.w : 0.f;
+  return L;
+}
+
+template <typename T, int KIND>
+__global__ __launch_bounds__(256) void k_box_iou(BoxIouArgs g) {
+  __shared__ float red[4];
+  __shared__ float4 l_p[4 * IOU_WCAP], l_t[4 * IOU_WCAP];
+  __shared__ int l_i[4 * IOU_WCAP];
+  __shared__ int wcnt[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const float npos = *g.npos + 1.f;
+  int seg, chunk;
+  chunk_lookup(g.p, LBOX_ROWS, blockIdx.x, seg, chunk);
+  const int rows = seg_rows(g.p, seg);
+  const int m0 = g.p.row_off[seg] + chunk * LBOX_ROWS;
+  const int nr = min(LBOX_ROWS, g.p.row_off[seg] + rows - m0);
+  const int A = g.A, A4 = A * 4, n = nr * A;
+  const int hw = g.p.H[seg] * g.p.W[seg];
+  int abase = 0;  // the level's first anchor (k_decode's indexing: anchors are per image)
+  for (int s = 0; s < seg; ++s) abase += g.p.H[s] * g.p.W[s] * A;
+  const float inv = 1.f / (4.f * npos), kw = g.iou_weight / npos;
+  const bool vec = g.vec != 0;
+  const T* P = (const T*)g.box;
+  T* D = (T*)g.dbox;
+  // anchor of slot i of this chunk (row m0 + i / A, anchor i % A)
+  auto anchor_of = [&](int r, int a) { return g.anchors + ((size_t)abase + (size_t)((m0 + r - g.p.row_off[seg]) % hw) * A + a) * 4; };
+  float hs = 0.f, ls = 0.f;
+  int cnt = 0;  // this wave's positives so far (wave-uniform)
+  for (int base = 0; base < n; base += 256) {
+    const int i = base + tid;
+    const bool valid = i < n;
+    bool pos = false;
+    int r = 0, a = 0;
+    float p[4], t[4], d[4];
+    if (valid) {
+      r = i / A;
+      a = i - r * A;
+      const size_t m = (size_t)(m0 + r);
+      ld4(P + m * g.ldb + 4 * a, vec, p);
+      ld4(g.box_t + (m * A + a) * 4, vec, t);
+      pos = g.mask[m * A + a] != 0;
+      hs += huber4(p, t, g.delta, inv, g.box_weight, d);
+    }
+    bool listed = false;
+    const unsigned long long bal = __ballot(pos);
+    if (bal) {
+      const int k = cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+      if (pos) {
+        if (k < IOU_WCAP) {
+          const int e = wave * IOU_WCAP + k;
+          l_i[e] = i;
+          l_p[e] = make_float4(p[0], p[1], p[2], p[3]);
+          l_t[e] = make_float4(t[0], t[1], t[2], t[3]);
+          listed = true;
+        } else {
+          float gi[4];
+          ls += iou_term<KIND>(p, t, anchor_of(r, a), gi);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) d[j] += kw * gi[j];
+        }
+      }
+      cnt += __popcll(bal);
+    }
+    if (valid && D && !listed) st4(D + (size_t)(m0 + r) * g.ldb + 4 * a, vec, d);
+  }
+  if (lane == 0) wcnt[wave] = cnt;
+  __syncthreads();
+  const bool any = (wcnt[0] | wcnt[1] | wcnt[2] | wcnt[3]) != 0;  // a block without positives adds no IoU term
+  const int c0 = min(wcnt[0], IOU_WCAP), c1 = c0 + min(wcnt[1], IOU_WCAP), c2 = c1 + min(wcnt[2], IOU_WCAP),
+            total = c2 + min(wcnt[3], IOU_WCAP);
+  for (int q = tid; q < total; q += 256) {  // total <= 4 * IOU_WCAP = 256: one trip
+    const int w = (q >= c0) + (q >= c1) + (q >= c2);
+    const int e = w * IOU_WCAP + q - (w == 0 ? 0 : w == 1 ? c0 : w == 2 ? c1 : c2);
+    const int i = l_i[e];
+    const float4 pv = l_p[e], tv = l_t[e];
+    const int r = i / A, a = i - r * A;
+    const float p[4] = {pv.x, pv.y, pv.z, pv.w}, t[4] = {tv.x, tv.y, tv.z, tv.w};
+    float d[4], gi[4];
+    huber4(p, t, g.delta, inv, g.box_weight, d);
+    ls += iou_term<KIND>(p, t, anchor_of(r, a), gi);
+    if (D) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) d[j] += kw * gi[j];
+      st4(D + (size_t)(m0 + r) * g.ldb + 4 * a, vec, d);
+    }
+  }
+  if (D && g.ldb > A4) {
+    const float z[4] = {0.f, 0.f, 0.f, 0.f};
+    if (vec) {  // ldb % 4 == 0: the pad is whole vectors
+      const int pv = (g.ldb - A4) / 4;
+      for (int e = tid; e < nr * pv; e += 256) {
+        const int r = e / pv;
+        st4(D + (size_t)(m0 + r) * g.ldb + A4 + 4 * (e - r * pv), true, z);
+      }
+    } else {
+      const int pad = g.ldb - A4;
+      for (int e = tid; e < nr * pad; e += 256) {
+        const int r = e / pad;
+        D[(size_t)(m0 + r) * g.ldb + A4 + (e - r * pad)] = from_f<T>(0.f);
+      }
+    }
+  }
+  hs = block_sum(hs, red);
+  ls = block_sum(ls, red);
+  if (tid == 0) {
+    atomicAdd(g.loss, hs * inv * g.box_weight);
+    if (g.parts) atomicAdd(g.parts + EDET_MAX_SEG + seg, hs * inv);
+    if (any) {
+      const float il = ls / npos;
+      atomicAdd(g.loss, g.iou_weight * il);
+      if (g.iou_parts) atomicAdd(g.iou_parts + seg, il);
+    }
+  }
+}
+
 // 16 mask bytes per thread and step, few blocks: the count ends in one same-address atomic
 // per block (exact: integer-valued floats far below 2^24)
 __global__ void k_count_pos(const uint8_t* mask, int64_t n, float* out) {
@@ -341,6 +630,51 @@ int edet_detection_loss(int dtype, const void* cls, int ldc, const void* box, in
   EDET_DTYPE_DISPATCH(dtype, T, {
     if (nb) EDET_LAUNCH(k_loss<T>, dim3(nb), dim3(256), 0, (hipStream_t)stream, g);
     return check_launch("edet detection_loss");
+  });
+}
+
+int edet_detection_loss_iou(int dtype, const void* cls, int ldc, const void* box, int ldb,
+                            const edet_pyramid* p, int A, int NC, const int32_t* cls_t,
+                            const float* box_t, const float* npos_sum, float alpha, float gamma,
+                            float delta, float box_weight, float focal_count_scale, void* dcls,
+                            void* dbox, float* loss, float* level_parts, const float* anchors,
+                            const uint8_t* mask, int iou_kind, float iou_weight, float* iou_parts,
+                            edet_stream_t stream) {
+  EDET_REQUIRE(cls && box && p && cls_t && box_t && npos_sum && loss, "detection_loss_iou: null argument");
+  EDET_REQUIRE(anchors && mask, "detection_loss_iou: null anchors or mask");
+  EDET_REQUIRE(ldc >= A * NC && ldb >= A * 4 && A > 0 && p->nseg >= 1 && p->nseg <= EDET_MAX_SEG,
+               "detection_loss_iou: bad strides");
+  EDET_REQUIRE(iou_kind >= EDET_IOU_LOSS_IOU && iou_kind <= EDET_IOU_LOSS_CIOU,
+               "detection_loss_iou: unknown iou_kind %d", iou_kind);
+  EDET_REQUIRE(iou_weight >= 0.f && iou_weight <= FLT_MAX,
+               "detection_loss_iou: iou_weight must be finite and >= 0");
+  // the class blocks of k_loss alone (its grid puts them first), then the whole box branch
+  LossArgs g{};
+  g.cls = cls; g.box = box; g.cls_t = cls_t; g.box_t = box_t; g.npos = npos_sum; g.dcls = dcls;
+  g.dbox = dbox; g.loss = loss; g.parts = level_parts; g.p = *p; g.ldc = ldc; g.ldb = ldb;
+  g.A = A; g.NC = NC; g.alpha = alpha; g.gamma = gamma; g.delta = delta; g.box_weight = box_weight;
+  g.count_scale = focal_count_scale > 0.f ? focal_count_scale : 1.f;
+  g.nb_cls = total_chunks(*p, LCLS_ROWS);
+  BoxIouArgs b{};
+  b.box = box; b.box_t = box_t; b.npos = npos_sum; b.anchors = anchors; b.mask = mask; b.dbox = dbox;
+  b.loss = loss; b.parts = level_parts; b.iou_parts = iou_parts; b.p = *p; b.ldb = ldb; b.A = A;
+  b.delta = delta; b.box_weight = box_weight; b.iou_weight = iou_weight;
+  const int nb_box = total_chunks(*p, LBOX_ROWS);
+  const hipStream_t st = (hipStream_t)stream;
+  EDET_DTYPE_DISPATCH(dtype, T, {
+    // one vector per anchor: four storage elements and the float4 of targets, all aligned
+    const uintptr_t va = 4 * sizeof(T) - 1;
+    b.vec = ldb % 4 == 0 && !((uintptr_t)box & va) && !((uintptr_t)dbox & va) && !((uintptr_t)box_t & 15);
+    if (g.nb_cls) EDET_LAUNCH(k_loss<T>, dim3(g.nb_cls), dim3(256), 0, st, g);
+    if (nb_box) {
+      switch (iou_kind) {
+        case EDET_IOU_LOSS_IOU: EDET_LAUNCH((k_box_iou<T, EDET_IOU_LOSS_IOU>), dim3(nb_box), dim3(256), 0, st, b); break;
+        case EDET_IOU_LOSS_GIOU: EDET_LAUNCH((k_box_iou<T, EDET_IOU_LOSS_GIOU>), dim3(nb_box), dim3(256), 0, st, b); break;
+        case EDET_IOU_LOSS_DIOU: EDET_LAUNCH((k_box_iou<T, EDET_IOU_LOSS_DIOU>), dim3(nb_box), dim3(256), 0, st, b); break;
+        default: EDET_LAUNCH((k_box_iou<T, EDET_IOU_LOSS_CIOU>), dim3(nb_box), dim3(256), 0, st, b); break;
+      }
+    }
+    return check_launch("edet detection_loss_iou");
   });
 }
 

@@ -461,6 +461,11 @@ class EfficientDetNetTrain(EfficientDetNet):
         # "per_class_topk" (the same with select="topk": the best candidates by score on overflow)
         # or "per_class_soft" (select="topk" with nms="soft": Gaussian Soft-NMS per class)
         self.detect_mode = "reference"
+        # IoU-family box regression term added to the fused loss (edet_detection_loss_iou): None
+        # (the reference's loss, Huber alone) or "iou" / "giou" / "diou" / "ciou", times
+        # iou_loss_weight.  Needs the anchors; iou_parts holds the per-level terms of the step
+        self.iou_loss_type = None
+        self.iou_loss_weight = 1.0
         # each data-parallel replica draws its own drop-connect masks (MirroredStrategy replicas
         # draw tf.random.uniform independently, drop_connect.py:13): fold the rank into the seed
         self.rank = rank
@@ -469,6 +474,7 @@ class EfficientDetNetTrain(EfficientDetNet):
         self.scalars = torch.zeros(8, dtype=torch.float32, device=dev)
         self.norm_partials = torch.zeros(2 * L.OPT_NORM_BLOCKS, dtype=torch.float64, device=dev)
         self.level_parts = torch.zeros(2 * L.MAX_SEG, dtype=torch.float32, device=dev)
+        self.iou_parts = torch.zeros(L.MAX_SEG, dtype=torch.float32, device=dev)
         self.step_counter = torch.zeros(1, dtype=torch.int32, device=dev)
         s = lr_schedule or {}
         sc = L.Sched()
@@ -525,7 +531,7 @@ class EfficientDetNetTrain(EfficientDetNet):
         x = data[0]
         B = x.shape[0]
         s = stream()
-        memset0_many([P.g, P.bn_tstats, self.scalars, self.level_parts])
+        memset0_many([P.g, P.bn_tstats, self.scalars, self.level_parts, self.iou_parts])
         pyr = Pyr(B, [self.level_hw[l] for l in self.levels])
         t = self._targets(data, pyr)
         # N+ = sum(masks) + 1 (the +1 is added by the loss kernel); padding rows are never read
@@ -541,20 +547,43 @@ class EfficientDetNetTrain(EfficientDetNet):
             sl = pyr.seg_slice(seg)
             L.call("edet_count_positives", vp(t.mask[sl]), pyr.seg_rows(seg) * self.A, vp(out), s)
 
+    def _detection_loss(self, kind, cls, box, pyr, t, npos, count_scale, dcls, dbox, loss, parts, iou_parts, s):
+        """The fused loss call of compute_step / test_step: edet_detection_loss, or with kind (from
+        _iou_loss_kind) not None edet_detection_loss_iou (the same arguments and the IoU term's)."""
+        args = (self.eng.dt, vp(cls.raw), cls.ld, vp(box.raw), box.ld, pyr.c, self.A, self.NC, vp(t.cls), vp(t.box),
+                vp(npos), float(self.cfg.alpha), float(self.cfg.gamma), 0.1, 50.0, count_scale, dcls, dbox, vp(loss),
+                vp(parts))
+        if kind is None:
+            L.call("edet_detection_loss", *args, s)
+            return
+        L.call("edet_detection_loss_iou", *args, vp(self.anchors.flat), vp(t.mask), kind, float(self.iou_loss_weight),
+               vp(iou_parts) if iou_parts is not None else None, s)
+
+    def _iou_loss_kind(self):
+        """EDET_IOU_LOSS_* of iou_loss_type (None: the plain loss); compute_step and test_step
+        check it before they run anything."""
+        if self.iou_loss_type is None:
+            return None
+        if self.iou_loss_type not in L.IOU_LOSS:
+            raise ValueError(f"iou_loss_type {self.iou_loss_type!r}: expected None, 'iou', 'giou', 'diou' or 'ciou'")
+        if self.anchors is None:
+            raise ValueError("iou_loss_type needs the model's anchors (construct it with anchors=...)")
+        return L.IOU_LOSS[self.iou_loss_type]
+
     def compute_step(self, data, t, pyr):
         """Forward, fused loss (fwd+bwd) and backward with N+ already global in scalars[5]."""
         eng = self.eng
         x = data[0]
         s = stream()
+        kind = self._iou_loss_kind()
         masks = self._make_masks(x.shape[0])
         eng.tape = Tape(eng, getattr(self, "grad_trace", None))
         cls, box, pyr2 = self._forward(x, True, masks)
         # fused focal + Huber loss: gradients are written in place over the logits.  The focal
         # mean runs over this replica's elements, so it is scaled by world_size to make the
         # replicas' sum the global-batch mean (SURVEY 8e).
-        L.call("edet_detection_loss", eng.dt, vp(cls.raw), cls.ld, vp(box.raw), box.ld, pyr.c, self.A, self.NC,
-               vp(t.cls), vp(t.box), vp(self.scalars[5:6]), float(self.cfg.alpha), float(self.cfg.gamma), 0.1, 50.0,
-               float(self.world_size), vp(cls.raw), vp(box.raw), vp(self.scalars[0:1]), vp(self.level_parts), s)
+        self._detection_loss(kind, cls, box, pyr, t, self.scalars[5:6], float(self.world_size), vp(cls.raw), vp(box.raw),
+                             self.scalars[0:1], self.level_parts, self.iou_parts, s)
         eng.tape.alias(cls, cls.raw, cls.ld)
         eng.tape.alias(box, box.raw, box.ld)
         eng.tape.backward()
@@ -611,6 +640,7 @@ class EfficientDetNetTrain(EfficientDetNet):
         reference's numpy_function call."""
         from . import metrics
         x, real_boxes, real_classes, yb, yc, ym = data
+        kind = self._iou_loss_kind()
         boxes_out, classes_out = self.call(x, training=False)
         cls, box, pyr = self.last_outputs
         t = Targets.from_reference(yb, yc, ym, pyr, self.A, self.eng.device)
@@ -618,9 +648,7 @@ class EfficientDetNetTrain(EfficientDetNet):
         sc = torch.zeros(8, dtype=torch.float32, device=self.eng.device)
         parts = torch.zeros(2 * L.MAX_SEG, dtype=torch.float32, device=self.eng.device)
         self._count_positives(t, pyr, sc[5:6], s)
-        L.call("edet_detection_loss", self.eng.dt, vp(cls.raw), cls.ld, vp(box.raw), box.ld, pyr.c, self.A, self.NC,
-               vp(t.cls), vp(t.box), vp(sc[5:6]), float(self.cfg.alpha), float(self.cfg.gamma), 0.1, 50.0, 1.0,
-               None, None, vp(sc[0:1]), vp(parts), s)
+        self._detection_loss(kind, cls, box, pyr, t, sc[5:6], 1.0, None, None, sc[0:1], parts, None, s)
         P = self.P  # _reg_l2_loss (efficientdet_net_train.py:21-28): the L2 prefix of the flat weights
         l2 = 4e-5 * 0.5 * float((P.w[: P.n_l2].double() ** 2).sum())
         loss = float(sc[0]) + l2
