@@ -454,6 +454,39 @@ int edet_generate_targets(const float* anchors, const edet_pyramid* p, int A,
                           const float* gt, const int32_t* gt_cls, const int32_t* n_gt,
                           int max_gt, float iou_thr, float* box_t, int32_t* cls_t,
                           uint8_t* mask, edet_stream_t stream);
+/* Target assignment with forced matching: the arg-max matcher with force_match_for_each_row of
+ * the published EfficientDet recipe's anchor labeler, opt-in next to edet_generate_targets (which
+ * stays the reference's rule).  Arguments as edet_generate_targets, plus force_match, gt_best
+ * (caller-owned scratch, [batch][max_gt] uint64, contents in and out unspecified; may be null
+ * with force_match == 0) and gt_anchor (output [batch][max_gt] int32, nullable).  anchors and
+ * box_t must be 16-byte aligned; an n_gt outside [0, max_gt] is clamped to it.
+ *
+ * Per image n, anchors are numbered i in the image's concatenated [level][H][W][A] order (the
+ * order of `anchors`), ground truths k < n_gt[n], and v(i,k) is the IoU of get_iou 'iou'
+ * (iou.py:27-69) of anchor i and box k in fp32 without contraction, as edet_generate_targets
+ * evaluates it.
+ *   1. per anchor: best_i = the first k attaining max_k v(i,k);
+ *      pos_i = n_gt > 0 && v(i,best_i) >= iou_thr  (edet_generate_targets' rule, bit for bit);
+ *   2. per ground truth (force_match != 0): f_k = the lowest i attaining max_i v(i,k), provided
+ *      that maximum is > 0.  A box for which no pair has v > 0 (a degenerate box, one that
+ *      overlaps no anchor, a NaN coordinate) forces nothing.  This departs on purpose from the TF
+ *      matcher, whose arg-max over an all-zero row forces anchor 0;
+ *   3. override: an anchor i with F_i = {k : f_k = i} non-empty is assigned min F_i instead of
+ *      best_i and is positive whatever iou_thr is (the lowest k wins, as in the TF matcher, whose
+ *      arg-max over the row indicators returns the first row);
+ *   4. box_t, cls_t and mask are encoded as edet_generate_targets encodes them (the same op
+ *      sequence; zeros and class 0 for non-positive anchors).  gt_anchor[n][k] = f_k, losers of
+ *      step 3 included; -1 where nothing was forced and for k >= n_gt[n].
+ * With force_match == 0 the three target outputs equal edet_generate_targets' bit for bit and
+ * gt_anchor is all -1.  No outcome depends on the order of atomic operations: the per-ground-
+ * truth arg-max is an integer max over the keys float_bits(v) << 32 | (0xFFFFFFFF - i).
+ * Launches: a clear of gt_best, the pair pass and the force pass (the pair pass alone with
+ * force_match == 0). */
+int edet_generate_targets_matched(const float* anchors, const edet_pyramid* p, int A,
+                                  const float* gt, const int32_t* gt_cls, const int32_t* n_gt,
+                                  int max_gt, float iou_thr, float* box_t, int32_t* cls_t,
+                                  uint8_t* mask, int force_match, uint64_t* gt_best,
+                                  int32_t* gt_anchor, edet_stream_t stream);
 int edet_decode_boxes(int dtype, const float* anchors, const edet_pyramid* p, int A,
                       const void* rel, int ld, float* out, edet_stream_t stream);
 

@@ -195,6 +195,7 @@ SIGNATURES = {
     "edet_onehot_to_index": [P, c_int64, c_int, P, P],
     "edet_anchor_boxes": [c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P, P],
     "edet_generate_targets": [P, PPyr, c_int, P, P, P, c_int, c_float, P, P, P, P],
+    "edet_generate_targets_matched": [P, PPyr, c_int, P, P, P, c_int, c_float, P, P, P, c_int, P, P, P],
     "edet_decode_boxes": [c_int, P, PPyr, c_int, P, c_int, P, P],
     "edet_detect_nms": [c_int, P, P, c_int, PPyr, c_int, c_int, c_int, c_float, c_float, P, P, P, P, P, P],
     "edet_detect_per_class": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float, c_float,

@@ -59,6 +59,9 @@ class Targets:
         self.box = torch.empty((pyr.rows, A, 4), dtype=torch.float32, device=device)
         self.cls = torch.empty((pyr.rows, A), dtype=torch.int32, device=device)
         self.mask = torch.empty((pyr.rows, A), dtype=torch.uint8, device=device)
+        # int32 [B, G] with force-match assignment: each ground truth's forced flat anchor (the
+        # image's concatenated [level][H][W][A] order) or -1; None otherwise
+        self.gt_anchor = None
 
     @staticmethod
     def from_reference(y_true_boxes, y_true_classes, y_true_masks, pyr: Pyr, A: int, device) -> "Targets":
@@ -79,6 +82,11 @@ class Targets:
 
 
 class Anchors:
+    # Force-match target assignment (include/edet.h, edet_generate_targets_matched): every ground
+    # truth also gets its best anchor whatever the IoU threshold, as the published recipe's
+    # arg-max matcher does.  The default of generate_targets[_batched]'s ``force_match`` argument.
+    force_match = False
+
     def __init__(self, min_level: int, max_level: int, image_size: Tuple[int, int], num_scales: int,
                  aspect_ratios: Sequence[Tuple[float, float]], anchor_scale: Union[float, List[float]],
                  device="cuda"):
@@ -128,8 +136,12 @@ class Anchors:
         return Pyr(batch, self.level_sizes)
 
     def generate_targets_batched(self, gt_boxes: torch.Tensor, gt_classes: torch.Tensor, n_gt: torch.Tensor,
-                                 iou_threshold: float = 0.5, pyr: Pyr = None) -> Targets:
-        """gt_boxes [B, G, 4] (y1,x1,y2,x2 pixels), gt_classes [B, G] int, n_gt [B] valid counts."""
+                                 iou_threshold: float = 0.5, pyr: Pyr = None, force_match: bool = None) -> Targets:
+        """gt_boxes [B, G, 4] (y1,x1,y2,x2 pixels), gt_classes [B, G] int, n_gt [B] valid counts.
+
+        ``force_match`` (None: the ``Anchors.force_match`` attribute) also assigns every ground
+        truth to the anchor it overlaps most, whatever the threshold (include/edet.h,
+        edet_generate_targets_matched); ``Targets.gt_anchor`` then holds the forced anchors."""
         B, G = gt_boxes.shape[0], gt_boxes.shape[1]
         pyr = pyr or self.pyramid(B)
         A = self.get_anchors_per_location()
@@ -139,18 +151,27 @@ class Anchors:
         gb = gt_boxes.to(self.device, torch.float32).contiguous()
         gc = gt_classes.to(self.device, torch.int32).contiguous()
         ng = n_gt.to(self.device, torch.int32).contiguous()
-        L.call("edet_generate_targets", vp(self.flat), pyr.c, A, vp(gb), vp(gc), vp(ng), max(G, 1),
-               float(iou_threshold), vp(t.box), vp(t.cls), vp(t.mask), stream())
+        if not (self.force_match if force_match is None else force_match):
+            L.call("edet_generate_targets", vp(self.flat), pyr.c, A, vp(gb), vp(gc), vp(ng), max(G, 1),
+                   float(iou_threshold), vp(t.box), vp(t.cls), vp(t.mask), stream())
+            return t
+        best = torch.empty((B, max(G, 1)), dtype=torch.int64, device=self.device)  # the kernels' key scratch
+        t.gt_anchor = torch.empty((B, max(G, 1)), dtype=torch.int32, device=self.device)
+        L.call("edet_generate_targets_matched", vp(self.flat), pyr.c, A, vp(gb), vp(gc), vp(ng), max(G, 1),
+               float(iou_threshold), vp(t.box), vp(t.cls), vp(t.mask), 1, vp(best), vp(t.gt_anchor), stream())
         return t
 
-    def generate_targets(self, boxes: torch.Tensor, classes: torch.Tensor, classes_num: int, iou_threshold=0.5):
+    def generate_targets(self, boxes: torch.Tensor, classes: torch.Tensor, classes_num: int, iou_threshold=0.5,
+                         force_match: bool = None):
         """Per-image form of anchors.py:91-138: returns per-level (boxes [H,W,A,4],
-        one-hot classes [H,W,A,classes_num], masks [H,W,A,1] bool)."""
+        one-hot classes [H,W,A,classes_num], masks [H,W,A,1] bool).  ``force_match`` as in
+        generate_targets_batched."""
         boxes = torch.as_tensor(boxes, dtype=torch.float32, device=self.device).reshape(-1, 4)
         classes = torch.as_tensor(classes, device=self.device).reshape(-1)
         n = boxes.shape[0]
         t = self.generate_targets_batched(boxes[None], classes[None].to(torch.int32),
-                                          torch.tensor([n], dtype=torch.int32), iou_threshold)
+                                          torch.tensor([n], dtype=torch.int32), iou_threshold,
+                                          force_match=force_match)
         A = t.A
         ob, oc, om = [], [], []
         for s, (fh, fw) in enumerate(self.level_sizes):

@@ -69,6 +69,18 @@ __device__ __forceinline__ void decode_one(const float* an, const T* rc, float* 
   o[3] = xc + w / 2.0f;
 }
 
+// Anchors._boxes_encoder (anchors.py:219-243) for one (anchor, ground truth) pair, k_targets' op
+// sequence: returns [ty, tx, th, tw] (csrc/match.hip: the pair pass and the force pass)
+__device__ __forceinline__ float4 encode_one(const float4 an, const float* gb) {
+  const float ycenter_a = (an.z + an.x) / 2.0f, xcenter_a = (an.w + an.y) / 2.0f;
+  float ha = an.z - an.x, wa = an.w - an.y;
+  const float ycenter = (gb[2] + gb[0]) / 2.0f, xcenter = (gb[3] + gb[1]) / 2.0f;
+  float h = gb[2] - gb[0], w = gb[3] - gb[1];
+  const float eps = 1e-8f;
+  ha = fmaxf(eps, ha); wa = fmaxf(eps, wa); h = fmaxf(eps, h); w = fmaxf(eps, w);
+  return make_float4((ycenter - ycenter_a) / ha, (xcenter - xcenter_a) / wa, logf(h / ha), logf(w / wa));
+}
+
 // flat candidate index within one image (levels concatenated, each [H][W][A]) -> pyramid row
 // and anchor
 __device__ __forceinline__ void cand_locate(const edet_pyramid& p, int A, int n, int i, int64_t& row, int& a) {
