@@ -600,6 +600,68 @@ int edet_detect_per_class_soft(int dtype, const float* anchors, const void* box,
                                float* out_boxes, int32_t* out_cls, float* out_scores, int32_t* out_count,
                                int32_t* out_total, int32_t* out_overflow, edet_stream_t stream);
 
+/* ---- COCO evaluation: bbox AP averaged over IoU 0.50:0.05:0.95, on the device ----
+ * The COCO bbox evaluation with area range "all", one detection cap and no crowd annotations;
+ * three entry points, no host synchronisation.  Everything is fp64 unless it says otherwise.
+ * Out of scope: crowd and ignore regions; the small, medium and large area ranges; AR at 1 and
+ * at 10 detections; masks.
+ *
+ * Inputs of one edet_eval_match call (a batch of images): detections in the layout
+ * edet_detect_per_class writes, boxes [batch][M][4] fp32 (y1, x1, y2, x2), classes [batch][M]
+ * int32, scores [batch][M] fp32, counts [batch]; ground truths gt_boxes [batch][G][4] fp32,
+ * gt_classes [batch][G] int32, n_gt [batch].  Class 0 is background and is never evaluated (a
+ * detection whose class is outside 0..NC-1 is recorded as class 0, a ground truth whose class is
+ * outside 1..NC-1 is skipped).  Rows past counts[b] or n_gt[b] are not read.
+ *
+ * IoU: from the fp32 coordinates, the differences formed in fp64: ih = max(0, min(y2) - max(y1)),
+ * iw likewise, inter = ih * iw, area = (y2 - y1) * (x2 - x1), uni = (area_d + area_g) - inter,
+ * iou = uni > 0 ? inter / uni : 0.  No contraction: a numpy restatement agrees bit for bit.
+ *
+ * Matching, per image, class c >= 1 and threshold t_k (k < EDET_EVAL_THRESHOLDS, iou_thr[k]:
+ * device doubles, np.linspace(0.5, 0.95, 10)), the thresholds independent of each other: the
+ * image's detections of class c by score descending, equal scores by lower row first; each takes,
+ * among the class-c ground truths of the image not yet matched at k, the one with the largest
+ * IoU provided iou >= min(t_k, 1 - 1e-10), on exactly equal IoU the higher ground-truth index;
+ * that ground truth is matched at k and bit k of the detection's TP mask is set.
+ *
+ * Records: image number i = image0 + b owns slots [i*M, i*M + counts).  Slot i*M + r takes the
+ * image's r-th detection in (class ascending, score descending, input row ascending) order and
+ * holds keys[slot] = class (7 bits) | score descending (32) | slot (25) and the 16-bit TP mask
+ * tp[slot]; the image's unused slots get the key ~0, which sorts last, and mask 0.  n_gt_class
+ * [NC] (int32) accumulates the ground truths per class.  Limits: NC <= 128, capacity_images * M
+ * <= 2^25, M <= 128, G <= 1024, image0 + batch <= capacity_images; each is refused with
+ * EDET_EINVAL before any launch.  table_pairs: the entries of the block's LDS table of
+ * same-class (detection, ground truth) IoUs, -1 for EDET_EVAL_TABLE_PAIRS (128 KiB); an image
+ * with more pairs recomputes its IoUs as it matches, with the same bits.
+ *
+ * edet_eval_sort sorts keys[0, n) ascending (class, then score descending, then slot) into
+ * scratch[0, npad), npad = n rounded up to 8192, the tail filled with ~0; scratch holds 2 * npad
+ * keys.  8192-key chunks are sorted in LDS, then merged by rank in ceil(log2(chunks)) rounds.
+ *
+ * edet_eval_ap, for class c with n = n_gt_class[c] > 0 and threshold k, walks the class's nd
+ * records of sorted[0, n_records) in order: tp_i = cumulative count of bit k, rc_i = tp_i / n,
+ * pr_i = tp_i / ((i + 1) + 2^-52); pr is made non-increasing from the end (pr_{i-1} =
+ * max(pr_{i-1}, pr_i)); for each rec_thr[r] (EDET_EVAL_RECALL_STEPS device doubles,
+ * np.linspace(0, 1, 101)) q_r = pr_j at the first j with rc_j >= rec_thr[r], 0 if there is none;
+ * ap[c][k] = (sum_r q_r) / 101 and ar[c][k] = rc_{nd-1}, or 0 when nd == 0 (a class with ground
+ * truths and no detections scores 0).  Class 0 and classes with n == 0 get -1 in both.  ap and
+ * ar are [NC][EDET_EVAL_THRESHOLDS] doubles; the reported AP is the mean of the valid ap[c][k],
+ * AP50 / AP75 the means of columns 0 and 5, AR the mean of the valid ar[c][k].  The sum of the
+ * 101 steps runs in a fixed order; no floating-point atomics anywhere. */
+#define EDET_EVAL_THRESHOLDS 10
+#define EDET_EVAL_RECALL_STEPS 101
+#define EDET_EVAL_MAX_DETS 128
+#define EDET_EVAL_MAX_GT 1024
+#define EDET_EVAL_MAX_CLASSES 128
+#define EDET_EVAL_TABLE_PAIRS 16384
+int edet_eval_match(const float* boxes, const int32_t* classes, const float* scores, const int32_t* counts,
+                    const float* gt_boxes, const int32_t* gt_classes, const int32_t* n_gt, int batch, int M, int G,
+                    int NC, const double* iou_thr, int image0, int capacity_images, int table_pairs, uint64_t* keys,
+                    uint16_t* tp, int32_t* n_gt_class, edet_stream_t stream);
+int edet_eval_sort(const uint64_t* keys, int64_t n, uint64_t* scratch, edet_stream_t stream);
+int edet_eval_ap(const uint64_t* sorted, int64_t n_records, const uint16_t* tp, const int32_t* n_gt_class, int NC,
+                 const double* rec_thr, double* ap, double* ar, edet_stream_t stream);
+
 /* ---- optimizer: L2 + clip_by_global_norm + SGD momentum + EMA, fused ----
  * scalars: [0] loss  [1] sum g^2  [2] sum w^2 (L2 params)  [3] gnorm  [4] lr  [5] npos
  *          [6] 1 when edet_opt_apply skipped a non-finite step (sched->skip_nonfinite), else 0

@@ -55,6 +55,10 @@ DETECT_MAX_CANDIDATES, DETECT_CHUNK_ROWS = 4096, 16  # EDET_DETECT_MAX_CANDIDATE
 OVERLAP = {"iou": 0, "diou": 1}  # EDET_OVERLAP_IOU, EDET_OVERLAP_DIOU
 SELECT = {"first": 0, "topk": 1}  # EDET_SELECT_FIRST, EDET_SELECT_TOPK
 IOU_LOSS = {"iou": 0, "giou": 1, "diou": 2, "ciou": 3}  # EDET_IOU_LOSS_IOU / GIOU / DIOU / CIOU
+# COCO evaluation (csrc/evalmap.hip): EDET_EVAL_THRESHOLDS, _RECALL_STEPS, _MAX_DETS, _MAX_GT, _MAX_CLASSES,
+# _TABLE_PAIRS; slot bits of a record key; keys of one sort chunk
+EVAL_THRESHOLDS, EVAL_RECALL_STEPS, EVAL_MAX_DETS, EVAL_MAX_GT, EVAL_MAX_CLASSES = 10, 101, 128, 1024, 128
+EVAL_TABLE_PAIRS, EVAL_SLOT_BITS, EVAL_CHUNK = 16384, 25, 8192
 
 
 def detect_scratch_bytes(batch: int, max_candidates: int, nbi: int, select: int = 0) -> int:
@@ -204,6 +208,9 @@ SIGNATURES = {
                                      c_float, c_int, c_int, P, P, P, P, P, P, P, P],
     "edet_detect_per_class_soft": [c_int, P, P, c_int, P, c_int, PPyr, c_int, c_int, c_int, c_int, c_float, c_int,
                                    c_int, c_double, c_double, P, P, P, P, P, P, P, P],
+    "edet_eval_match": [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, P, P],
+    "edet_eval_sort": [P, c_int64, P, P],
+    "edet_eval_ap": [P, c_int64, P, P, c_int, P, P, P, P],
     "edet_opt_norm": [P, P, c_int64, c_int64, PSched, P, P, P, P],
     "edet_opt_apply": [P, P, P, P, c_int64, c_int64, PSched, P, P, c_int, P, P, P],
     "edet_cast_f32": [c_int, P, P, c_int64, P],

@@ -24,6 +24,7 @@
 // sums): the candidate list, and so every output, is a function of the inputs alone.
 #pragma clang fp contract(off)
 #include <float.h>
+#include "blockops.hpp"
 #include "boxes.hpp"
 
 namespace edet {
@@ -32,16 +33,7 @@ constexpr int DET_CH = EDET_DETECT_CHUNK_ROWS;  // pyramid rows per scan block
 constexpr int DET_THREADS = 256;                // scan block (4 waves)
 constexpr uint64_t KEY_SENTINEL = ~0ull;        // sorts after every real key
 
-// fp32 -> uint32 whose unsigned order is the DESCENDING float order (an ascending sort of the
-// keys then yields logit descending), and back
-__device__ __forceinline__ uint32_t desc_bits(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return ~(u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u));
-}
-__device__ __forceinline__ float desc_float(uint32_t k) {
-  k = ~k;
-  return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu));
-}
+// (desc_bits / desc_float, the order-preserving float key, and bitonic_sort: blockops.hpp)
 // scan key: class (8) | logit, descending (32) | anchor index in the image (24)
 __device__ __forceinline__ uint64_t make_key(int c, float v, int i) {
   if (v == 0.f) v = 0.f;  // -0 and +0 are one score
@@ -503,20 +495,6 @@ __global__ __launch_bounds__(DET_THREADS) void k_sel_write(const T* cls, int ldc
           pe += e ? 1 : 0;
         }
       }
-    }
-  }
-}
-
-// ascending bitonic sort of P (a power of two) keys in LDS by the whole block
-__device__ __forceinline__ void bitonic_sort(uint64_t* k, int P) {
-  for (int kk = 2; kk <= P; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < (P >> 1); t += blockDim.x) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const uint64_t a = k[i], b = k[l];
-        if ((a > b) == ((i & kk) == 0)) { k[i] = b; k[l] = a; }
-      }
-      __syncthreads();
     }
   }
 }

@@ -10,6 +10,7 @@
 //   k_force        one block per image: keys -> forced anchors, lowest k wins an anchor, rewrite
 //                  of the forced anchors' targets
 #pragma clang fp contract(off)
+#include "blockops.hpp"
 #include "boxes.hpp"
 
 #include <algorithm>
@@ -18,8 +19,6 @@ namespace edet {
 
 constexpr int MT_THREADS = 256;  // threads of a k_match / k_force block
 constexpr int MT_TILE = 128;     // ground truths staged in LDS at a time
-
-typedef unsigned long long u64;
 
 // index of flat anchor i of image n in the [rows][A] target arrays: (pyramid row) * A + a.
 // Compile-time segment indices only, so the pyramid stays in scalar registers.
@@ -40,30 +39,8 @@ __device__ __forceinline__ int64_t target_index(const edet_pyramid& p, int A, in
 // forced anchor of a ground truth from its key: float_bits(v) << 32 | (0xFFFFFFFF - i), 0 = none
 __device__ __forceinline__ int key_anchor(u64 key) { return key ? (int)(0xFFFFFFFFu - (uint32_t)key) : -1; }
 
-template <int CTRL>
-__device__ __forceinline__ uint32_t dpp_u32(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
-}
-// Max of an unsigned word over the wave, result in every lane: four DPP steps within the 16-lane
-// rows and the two row swaps of gfx950, all VALU (the shuffle form is six ds_bpermute round trips)
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  v = max(v, dpp_u32<0xB1>(v));   // quad_perm [1,0,3,2]: lane ^ 1
-  v = max(v, dpp_u32<0x4E>(v));   // quad_perm [2,3,0,1]: lane ^ 2
-  v = max(v, dpp_u32<0x141>(v));  // row_half_mirror: the other quad of the 8-lane half
-  v = max(v, dpp_u32<0x140>(v));  // row_mirror: the other half of the row
-  const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-  v = max(r[0], r[1]);
-  const auto h = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-  return max(h[0], h[1]);
-}
+// (wave_max_u32 / wave_max_u64, the DPP reductions of the keys: blockops.hpp)
 __device__ __forceinline__ u64 umax64(u64 a, u64 b) { return a > b ? a : b; }
-// Max of a 64-bit key over the wave as two word reductions: the largest high word, then the
-// largest low word among the lanes that hold it (a 64-bit compare-and-select per step cost three
-// times the instructions; measured)
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-  const uint32_t hi = (uint32_t)(v >> 32), top = wave_max_u32(hi);
-  return ((u64)top << 32) | wave_max_u32(hi == top ? (uint32_t)v : 0u);
-}
 
 __global__ void k_match_clear(u64* p, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * MT_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * MT_THREADS) p[i] = 0;

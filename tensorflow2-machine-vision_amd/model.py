@@ -630,6 +630,31 @@ class EfficientDetNetTrain(EfficientDetNet):
         memset0(self.P.v)
         memset0(self.step_counter)
 
+    def _detect(self, boxes_out, classes_out, max_output_size=None):
+        """The detect_mode dispatch: (boxes [B,max,4], class ids, scores [B,max], counts [B]) on
+        the device.  max_output_size None: each mode's own default."""
+        kw = {} if max_output_size is None else {"max_output_size": max_output_size}
+        if self.detect_mode in ("per_class", "per_class_topk", "per_class_soft"):
+            sel = "first" if self.detect_mode == "per_class" else "topk"
+            nms = "soft" if self.detect_mode == "per_class_soft" else "hard"
+            return self.anchors.detect_per_class(boxes_out, classes_out, select=sel, nms=nms, **kw)[:4]
+        if self.detect_mode == "reference":
+            return self.anchors.detect(self.anchors.convert_outputs_boxes(boxes_out), classes_out, **kw)
+        raise ValueError(f"detect_mode {self.detect_mode!r}: expected 'reference', 'per_class', "
+                         f"'per_class_topk' or 'per_class_soft'")
+
+    def eval_step(self, data, evaluator):
+        """One batch of the COCO evaluation (metrics.CocoEvaluator): inference-mode forward, the
+        detect_mode post-processing capped at the evaluator's max_dets, and evaluator.add, all
+        on the device: no host copy and no synchronisation.
+
+        data = (x, gt_boxes [B,G,4], gt_classes [B,G], n_gt [B]); evaluator.summarize() after the
+        last batch gives the figures."""
+        x, gt_boxes, gt_classes, n_gt = data
+        boxes_out, classes_out = self.call(x, training=False)
+        ob, oc, os_, cnt = self._detect(boxes_out, classes_out, evaluator.max_dets)
+        evaluator.add(ob, oc, os_, cnt, torch.as_tensor(gt_boxes), torch.as_tensor(gt_classes), torch.as_tensor(n_gt))
+
     def test_step(self, data):
         """test_step (efficientdet_net_train.py:135-169): inference-mode forward, the same loss
         (forward only), decode + DIoU-NMS per image on the GPU, and the reference's per-image
@@ -652,15 +677,7 @@ class EfficientDetNetTrain(EfficientDetNet):
         P = self.P  # _reg_l2_loss (efficientdet_net_train.py:21-28): the L2 prefix of the flat weights
         l2 = 4e-5 * 0.5 * float((P.w[: P.n_l2].double() ** 2).sum())
         loss = float(sc[0]) + l2
-        if self.detect_mode in ("per_class", "per_class_topk", "per_class_soft"):
-            sel = "first" if self.detect_mode == "per_class" else "topk"
-            nms = "soft" if self.detect_mode == "per_class_soft" else "hard"
-            ob, oc, os_, cnt = self.anchors.detect_per_class(boxes_out, classes_out, select=sel, nms=nms)[:4]
-        elif self.detect_mode == "reference":
-            ob, oc, os_, cnt = self.anchors.detect(self.anchors.convert_outputs_boxes(boxes_out), classes_out)
-        else:
-            raise ValueError(f"detect_mode {self.detect_mode!r}: expected 'reference', 'per_class', "
-                             f"'per_class_topk' or 'per_class_soft'")
+        ob, oc, os_, cnt = self._detect(boxes_out, classes_out)
         ob, oc, os_, cnt = ob.cpu().numpy(), oc.cpu().numpy(), os_.cpu().numpy(), cnt.cpu().numpy()
         rb = np.asarray(real_boxes.cpu() if isinstance(real_boxes, torch.Tensor) else real_boxes, np.float64)
         rc = np.asarray(real_classes.cpu() if isinstance(real_classes, torch.Tensor) else real_classes, np.float64)
